@@ -9,13 +9,23 @@ scale — with synthetic client inputs from the reference harness's seeded gener
 A step = one batch of `--slots` Groth16 proofs (ABC, 3x coset NTT, 4 G1 + 1 G2 MSM, assembly),
 one per in-flight proof slot, from device-resident witnesses with the proving key resident in HBM;
 K steps = K x slots proofs pushed through the batch prover in one call (the slots stay full across
-step boundaries).  r, s come from the OS CSPRNG on the host and are passed in, so every timed
-proof is checked after the timed region: all of them by the GPU batch verifier, and the first one
-bit-for-bit against the C oracle inside the cpu_baseline leg.  Multi-GPU: one process per GPU,
-independent proofs per rank (weak scaling, no collective on the data path); the barrier /
-max-over-ranks timing uses torch.distributed.
+step boundaries).  r, s come from a seeded generator on the host (RS_SEED: the same arguments give
+the same inputs, hence the same proofs, run after run and build after build) and are passed in.
+Multi-GPU: one process per GPU, independent proofs per rank (weak scaling, no collective on the
+data path); the barrier / max-over-ranks timing uses torch.distributed.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md §6 for the roofline definitions).
+A plain run does what the headline figure needs and no more: setup (circuit, dev zkey, key load,
+device-resident witnesses), W warm-up steps, K timed steps, the outputs if --dump-outputs DIR is
+given (the last timed step's proofs as DIR/proofs.npy), the line.  --full adds every other leg and
+check, as one run: config 5 (strong and weak), one proof alone, every timed proof through the GPU
+batch verifier, the serialized per-kernel pass behind the roofline and the stage times, the
+input.json -> proof leg, the 2^19-domain circuit, the dataset commitment, the split proof
+(--split-proofs N), the `npx snarkjs groth16 prove` CLI leg, and the C oracle on the host cores,
+which also checks the first timed proof bit for bit.  The legs' own options (--e2e-steps,
+--c5-rounds, ...) size or skip them under --full and are ignored without it.
+
+Prints ONE JSON line on rank 0 (see DESIGN.md §6 for the roofline definitions); the fields of the
+legs that did not run are null.
 """
 
 from __future__ import annotations
@@ -97,12 +107,28 @@ def cpu_baseline_leg(zk: bytes, wt: bytes, rs: bytes, seconds_budget=20.0):
     return cbaseline.time_prove(zk, wt, seconds_budget, rs)
 
 
-def draw_rs(n):
-    """n x (r || s), 32 B little-endian each, uniform below the BN254 scalar order (OS CSPRNG)."""
-    import secrets
+RS_SEED = 0x5EED5   # the blinding factors of the timed proofs: fixed, so two runs prove the same thing
+
+
+def draw_rs(n, seed=RS_SEED):
+    """n x (r || s), 32 B little-endian each, uniform below the BN254 scalar order, from a generator
+    seeded with `seed` (a benchmark input, reproducible on purpose; a real prover draws them from
+    the OS CSPRNG, as the library does when it is passed none)."""
+    import random
     from zkfl.field import R
-    return b"".join(secrets.randbelow(R).to_bytes(32, "little") + secrets.randbelow(R).to_bytes(32, "little")
+    rng = random.Random(seed)
+    return b"".join(rng.randrange(R).to_bytes(32, "little") + rng.randrange(R).to_bytes(32, "little")
                     for _ in range(n))
+
+
+def dump_outputs(out_dir, name, proofs):
+    """--dump-outputs: what the timed prove_batch call returned for its last step, as
+    DIR/<name>.npy -- one row per proof, its 256 bytes (A | B | C, little-endian coordinates) as
+    float32 values 0..255, which holds every byte exactly."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arr = np.frombuffer(b"".join(proofs), dtype=np.uint8).reshape(len(proofs), 256).astype(np.float32)
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def timed_run(key, warm_w, steps_w, rs, ctx, dist):
@@ -836,15 +862,16 @@ def launch_ranks(n):
 
 
 def report(args, world, elapsed, n_timed_all, verified_all, prof, nprof, key, config, extra):
-    """The bench JSON line (rank 0).  `extra`: roofline / end_to_end / c5 / cpu_baseline fields."""
-    stage_ms = stage_times(prof, nprof)
+    """The bench JSON line (rank 0).  `extra`: roofline / end_to_end / c5 / cpu_baseline fields.
+    prof None (a run without the serialized per-kernel pass): no roofline, no stage times."""
+    stage_ms = stage_times(prof, nprof) if prof else None
     line = {
         "metric": METRIC, "value": round(n_timed_all / elapsed, 4), "unit": "proofs/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
         "data": "synthetic (reference harness seeded client generator)",
         "config": config, "proofs_timed": n_timed_all, "verified": verified_all,
-        "roofline": roofline(prof, key, nprof=nprof) if key is not None else None,
+        "roofline": roofline(prof, key, nprof=nprof) if key is not None and prof else None,
         "stage_ms_isolated_per_proof": stage_ms,
     }
     line.update(extra)
@@ -869,9 +896,16 @@ def main():
     ap.add_argument("--steps", type=int, default=16, help="timed steps (one step = --slots proofs)")
     ap.add_argument("--warmup", type=int, default=2, help="untimed steps")
     ap.add_argument("--circuit", default="M", choices=sorted(CIRCUITS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--slots", type=int, default=20, help="proofs in flight per GPU (one HIP stream each)")
     ap.add_argument("--clients", type=int, default=4, help="distinct synthetic client witnesses, cycled")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg and check (config 5, one proof alone, GPU verification of the "
+                         "timed proofs, roofline pass, input.json leg, extra circuit, dataset commitment, CLI leg, "
+                         "CPU baseline + oracle check); the options below apply to this mode only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's proofs to DIR/proofs.npy "
+                         "(float32, one row of 256 byte values per proof; proofs_rank<r>.npy with several ranks)")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--e2e-steps", type=int, default=16, help="steps of the input.json -> proof leg (0: skip)")
     # 16 rounds: at 8 (~75 ms timed) the first round's ramp (slots filling, the first witness group)
     # weighed 1/8 -- bench 1751-1828 against 1900-1915 from tools/c5_probe.py's 16 rounds, same box
@@ -939,7 +973,7 @@ def main():
     # their scratch) stay out of its way (the same c5 code read 1894 proofs/s alone and 1440 after
     # the main legs on one box, round 4)
     c5 = c5w = None
-    if args.c5_rounds:
+    if args.full and args.c5_rounds:
         c5, c5w = c5_leg(ctx, rank, world, args.c5_rounds, args.c5_slots, dist, args.c5_weak_rounds)
         log(f"[bench r{rank}] config 5: {c5}; weak: {c5w}")
     t0 = time.perf_counter()
@@ -951,35 +985,42 @@ def main():
     t0 = time.perf_counter()
     res = wp.compute_resident(key, inputs)      # GPU witness generation straight into HBM
     log(f"[bench r{rank}] {len(res)} client witnesses on the GPU ({(time.perf_counter() - t0) * 1e3:.1f} ms)")
-    wts = wp.compute(inputs)                    # host .wtns images: public signals + the oracle check
+    wts = wp.compute(inputs) if args.full else None     # host .wtns images: public signals + the oracle check
     n_timed = args.steps * args.slots
     steps_w = [res[i % len(res)] for i in range(n_timed)]
     warm_w = [res[i % len(res)] for i in range(args.warmup * args.slots)]
-    rs = draw_rs(n_timed)
+    rs = draw_rs(n_timed, RS_SEED + rank)
 
-    # one proof alone first, on the idle chip a CLI invocation meets (measured after the 20-slot
-    # run it read 4.49 / 4.64 ms on two boxes, against 4.06-4.22 ms for tools/ko_probe.py --latency
-    # on a fresh process on others)
-    lat = latency_leg(key, res)
-    log(f"[bench r{rank}] one proof alone: {lat}")
+    lat = None
+    if args.full:
+        # one proof alone first, on the idle chip a CLI invocation meets (measured after the 20-slot
+        # run it read 4.49 / 4.64 ms on two boxes, against 4.06-4.22 ms for tools/ko_probe.py --latency
+        # on a fresh process on others)
+        lat = latency_leg(key, res)
+        log(f"[bench r{rank}] one proof alone: {lat}")
     elapsed, proofs, busy = timed_run(key, warm_w, steps_w, rs, ctx, dist)
     host_cpu = {"main": round(busy * 1e3 / n_timed, 3)}
     assert len(proofs) == n_timed and all(len(p) == 256 for p in proofs)
-    pubs = [w[76 + 32:76 + 32 * (1 + key.n_public)] for w in wts]   # wtns v2: header 76 B, wire 0 = 1
-    verified = verify_all(ctx, zk, proofs, lambda i: pubs[i % len(pubs)])
-    log(f"[bench r{rank}] {n_timed} proofs in {elapsed:.3f} s; GPU batch verifier: {verified}/{n_timed} valid")
-    verified_all = _sum_over_ranks(verified, dist)
-    if verified_all != n_timed * world:
-        raise SystemExit(f"[bench r{rank}] {n_timed * world - verified_all} timed proofs do not verify")
-    prof, nprof = roofline_pass(key, ctx, res, args.slots)
+    log(f"[bench r{rank}] {n_timed} proofs in {elapsed:.3f} s")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "proofs" if world == 1 else f"proofs_rank{rank}", proofs[-args.slots:])
     kinfo = KeyInfo(key.n_vars, key.n_public, key.domain_size)
-    e2e = None
-    if args.e2e_steps:
+    pubs = verified_all = prof = e2e = None
+    nprof = 0
+    if args.full:
+        pubs = [w[76 + 32:76 + 32 * (1 + key.n_public)] for w in wts]   # wtns v2: header 76 B, wire 0 = 1
+        verified = verify_all(ctx, zk, proofs, lambda i: pubs[i % len(pubs)])
+        log(f"[bench r{rank}] GPU batch verifier: {verified}/{n_timed} valid")
+        verified_all = _sum_over_ranks(verified, dist)
+        if verified_all != n_timed * world:
+            raise SystemExit(f"[bench r{rank}] {n_timed * world - verified_all} timed proofs do not verify")
+        prof, nprof = roofline_pass(key, ctx, res, args.slots)
+    if args.full and args.e2e_steps:
         e2e = end_to_end_leg(key, wp, wprog.compile_program(b), [json.dumps(x) for x in input_objs], args.slots,
                              args.e2e_steps, ctx, dist, zk, pubs)
         log(f"[bench r{rank}] end to end: {e2e}")
     split_wts = None
-    if args.split_proofs:
+    if args.full and args.split_proofs:
         # every shard of a split proof needs the SAME witness: rank 0's first two clients on all ranks
         common = [wprog.input_bytes(b, clients.Client(c + 1, batch, dim, depth, clients.JsLcg(12345 + c))
                                     .training_input(batch, precision, 100000000)[0]) for c in range(2)]
@@ -989,16 +1030,16 @@ def main():
     wp.close()
     key.set_slots(1)
     extra = None
-    if args.extra_circuit and args.extra_circuit != "none" and args.extra_circuit != args.circuit:
+    if args.full and args.extra_circuit and args.extra_circuit != "none" and args.extra_circuit != args.circuit:
         extra = extra_circuit_leg(ctx, rank, world, args.extra_circuit, args.extra_steps, args.slots, dist)
         log(f"[bench r{rank}] {args.extra_circuit}: {extra}")
     merkle = None
-    if args.merkle_log2n:
+    if args.full and args.merkle_log2n:
         merkle = merkle_leg(ctx, rank, args.merkle_log2n)
         log(f"[bench r{rank}] dataset commitment: {merkle}")
     split_res = {"skipped": "off by default (--split-proofs N runs it): one proof split over the ranks is bounded "
                             "by one GPU's latency schedule (DESIGN.md §7)"}
-    if args.split_proofs:  # last: the other legs never run beside a second (shard) key
+    if args.full and args.split_proofs:  # last: the other legs never run beside a second (shard) key
         split_res = split_leg(ctx, rank, world, zk, split_wts, key, dist, args.split_proofs)
         log(f"[bench r{rank}] split proof: {split_res}")
     for tag, leg in (("c5", c5), ("c5_weak", c5w)):
@@ -1006,7 +1047,7 @@ def main():
             host_cpu[tag] = leg["host_cpu_ms_per_proof"]
     host = host_report(rank, device, dist, pin, host_cpu)   # collective: every rank
     cli = None
-    if args.cli_runs and world == 1:
+    if args.full and args.cli_runs and world == 1:
         try:
             cli = cli_leg(ctx, args.cli_runs)
         except Exception as e:  # noqa: BLE001
@@ -1014,7 +1055,7 @@ def main():
         log(f"[bench r{rank}] cli prove: {cli}")
     if rank == 0:
         cpu, oracle_match = None, None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cpu, ref = cpu_baseline_leg(zk, wts[0], rs[:64])
                 oracle_match = ref == proofs[0]
@@ -1028,7 +1069,7 @@ def main():
                   "parallelism": f"replicas{world}", "slots_in_flight": args.slots,
                   "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))}
         line = report(args, world, elapsed, n_timed * world, verified_all, prof, nprof, kinfo, config,
-                      {"n_gpus": devices_used, "ranks": world, "build_id": build_id,
+                      {"n_gpus": devices_used, "ranks": world, "full": args.full, "build_id": build_id,
                        "build_matches_sources": build_id == source_id, "oracle_match": oracle_match,
                        "end_to_end": e2e, "c5": c5, "c5_weak": c5w, "extra_circuit": extra,
                        "latency_single_proof": lat, "dataset_commit": merkle, "split_proof": split_res,

@@ -34,7 +34,7 @@ def test_two_ranks_real_prover_one_device(tmp_path):
     env["ZKFL_HW_QUEUES"] = "12"        # two processes share the device's hardware queues
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--slots", "4", "--e2e-steps", "1",
+           "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--slots", "4", "--e2e-steps", "1",
            "--c5-rounds", "2", "--c5-weak-rounds", "1", "--extra-circuit", "none", "--merkle-log2n", "0",
            "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
@@ -66,7 +66,7 @@ def test_two_ranks_without_launcher(tmp_path):
     env["ZKFL_HW_QUEUES"] = "12"
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "1", "--warmup", "1",
            "--slots", "2", "--e2e-steps", "0", "--c5-rounds", "0", "--merkle-log2n", "0", "--extra-circuit", "none",
            "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/sq
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -s KILL 240 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU --kernel-trace -d "$OUT/db" -o run -- python3 "$R/bench.py" --steps 4 --warmup 1 --slots 1 --no-cpu-baseline > "$OUT/bench.log" 2>&1
+timeout -s KILL 240 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU --kernel-trace -d "$OUT/db" -o run -- python3 "$R/bench.py" --full --steps 4 --warmup 1 --slots 1 --no-cpu-baseline > "$OUT/bench.log" 2>&1
 python3 - "$OUT/db/run_results.db" > "$OUT/sq_counters.txt" <<'PY'
 import sqlite3, sys
 c = sqlite3.connect(sys.argv[1])
