@@ -1,10 +1,10 @@
-"""C-ABI object lifetimes and a slot-stream configuration on an MI355X (-m gpu).
+"""C-ABI object lifetimes and serialized profiling on a two-slot key on an MI355X (-m gpu).
 
 * zkfl_ctx_destroy may come before zkfl_key_free / zkfl_wprog_free / zkfl_witness_free (the N-API
   finalizers run in an unspecified order): the context is reference-counted by its keys and
-  witness programs (csrc/zkfl.hip ctx_retain / ctx_release), so every order is safe.
-* ZKFL_SLOT_STREAMS=2 with serialized profiling: the slot owns a second stream but the B2 MSM
-  shares B1's sort on the main stream, so k_proof_start must empty the G2 tail too.
+  witness programs (csrc/objects.h, csrc/zkfl.hip ctx_retain / ctx_release), so every order is safe.
+* Serialized profiling on a two-slot key: the B2 MSM shares B1's sort on the slot's stream, so
+  k_proof_start must empty the G2 tail too.
 """
 import ctypes as C
 import os
@@ -63,8 +63,8 @@ def test_ctx_destroy_in_any_order(gpu_ctx, order):
         assert k2.prove(wt, RS)[0] == ref
 
 
-def test_slot_streams_2_serialized_profiling_parity(tmp_path):
-    """ZKFL_SLOT_STREAMS=2 + serialized profiling (bench.py's stage pass on a two-stream slot): the
+def test_slot_streams_serialized_profiling_parity(tmp_path):
+    """Serialized profiling (bench.py's stage pass) on a two-slot key, three proofs, two passes: the
     proofs equal the oracle's, including pi_B (the G2 tail emptied by k_proof_start)."""
     script = tmp_path / "s2.py"
     script.write_text(f"""
@@ -94,6 +94,5 @@ with native.Context(0) as ctx:
     key.close()
 print("ok")
 """)
-    env = dict(os.environ, ZKFL_SLOT_STREAMS="2")
-    p = subprocess.run([sys.executable, "-u", str(script)], capture_output=True, text=True, timeout=300, env=env)
+    p = subprocess.run([sys.executable, "-u", str(script)], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and p.stdout.strip().endswith("ok"), p.stdout + p.stderr

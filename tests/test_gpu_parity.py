@@ -426,6 +426,36 @@ def test_batch_equals_single_proofs(gpu_ctx, monkeypatch, width):
     key.close()
 
 
+def test_unshared_b2_sort_matches_oracle(gpu_ctx):
+    """A key whose B1 and B2 index maps differ: one B1 point (zkey section 6) zeroed, so the loader
+    drops that wire from B1 only and B2 runs as an MSM of its own (own sort, own tail) instead of on
+    B1's sorted pairs.  Honest keys never take this path.  Three proofs on two slots, two passes (the
+    second reuses the first's buckets), against the oracle on the modified key (an all-zero point is
+    infinity there too)."""
+    from zkfl import native, zkey
+    b, zk = _setup(gpu_ctx, "poseidon_hash2")
+    ws = [ow.evaluate(b, {"left": l, "right": r}) for l, r in ((1, 2), (3, 4), (5, 6))]
+    _, secs = og.read_binfile(zk, b"zkey")
+    o6, o7 = secs[6][0][0], secs[7][0][0]
+    # the zeroed wire: its B2 point is not infinity and its witness values are non-zero
+    wire = next(i for i in range(len(ws[0])) if any(zk[o7 + 128 * i:o7 + 128 * i + 128]) and all(w[i] for w in ws))
+    mod = zk[:o6 + 64 * wire] + bytes(64) + zk[o6 + 64 * wire + 64:]
+    z = og.parse_zkey(mod)
+    assert z["B1"][wire] is None and z["B2"][wire] is not None
+    rs = [(0x1234567 + j, 0x7654321 + j) for j in range(3)]
+    refs = [og.proof_bytes(og.prove(z, w, r=r, s=s)) for w, (r, s) in zip(ws, rs)]
+    assert refs[0] != og.proof_bytes(og.prove(og.parse_zkey(zk), ws[0], r=rs[0][0], s=rs[0][1]))
+    key = native.ProvingKey(gpu_ctx, mod)
+    key.set_slots(2)
+    wts = [key.upload(zkey.wtns_bytes(w)) for w in ws]
+    for rep in range(2):
+        got = key.prove_batch(wts, b"".join(_le(r) + _le(s) for r, s in rs))
+        assert got == refs, (rep, [g == r for g, r in zip(got, refs)])
+    for w in wts:
+        w.close()
+    key.close()
+
+
 def test_node_snarkjs_cli_prove(gpu_ctx, tmp_path):
     """`node snarkjs_shim.js groth16 prove zkey wtns proof.json public.json` — the reference's
     execSync line (tests/full_system_simulation.mjs:773-776) through N-API -> C ABI -> HIP."""

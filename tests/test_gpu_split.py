@@ -128,7 +128,7 @@ def test_assemble_rejects_bad_coordinates(gpu_ctx):
     assert out == [bytes(256)]
 
 
-# word offsets of a part's points (csrc/zkfl.hip PART_OFF): A' 0, B1' 32, B2' 64 (G2), C' 128, H 160;
+# word offsets of a part's points (csrc/assemble.hip PART_OFF): A' 0, B1' 32, B2' 64 (G2), C' 128, H 160;
 # a G1 point is X | Y | ZZ | ZZZ, 8 words each, standard form
 @pytest.mark.parametrize("case", ["zz_without_zzz", "zzz_without_zz", "off_curve", "zz3_ne_zzz2", "g2_off_curve"])
 def test_assemble_rejects_malformed_points(gpu_ctx, case):
@@ -162,7 +162,7 @@ def test_assemble_rejects_malformed_points(gpu_ctx, case):
 
 @pytest.mark.parametrize("case", ["double", "cancel"])
 def test_assemble_exceptional_sums(gpu_ctx, case):
-    """The assembly's quad operations run on lazy values (csrc/zkfl.hip Q29: below small multiples
+    """The assembly's quad operations run on lazy values (csrc/assemble.hip Q29: below small multiples
     of p, is_zero<K> over 0, p, .., (K-1) p): equal points in different XYZZ scalings must still
     take the doubling branch, opposite ones the infinity branch.  double: A' = B1' = P (scalings
     3 and 7), r = s, C' = H = Q (scalings 2 and 11); cancel: B1' = -A', H = -C'."""

@@ -283,6 +283,12 @@ bool fr_lt_r(const uint32_t v[8]) {
   return false;
 }
 
+bool fq_lt_q(const uint32_t v[8]) {
+  for (int i = 7; i >= 0; i--)
+    if (v[i] != Q_LIMBS[i]) return v[i] < Q_LIMBS[i];
+  return false;
+}
+
 int binfile_sections(const uint8_t* buf, size_t len, const char magic[4], std::vector<Section>& secs,
                      std::string& err) {
   if (!buf || len < 12) return bad(err, ZKFL_E_FORMAT, "file too short");

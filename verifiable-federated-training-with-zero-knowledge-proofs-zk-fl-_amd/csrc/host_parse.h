@@ -35,7 +35,7 @@ struct WtnsView {
 int wtns_parse(const uint8_t* buf, size_t len, WtnsView& out, std::string& err);
 
 // groth16 .zkey -> header, point sections, and the QAP coefficients as CSR rows (A rows then B
-// rows over one term array) with the packed-dictionary encoding of csrc/zkfl.hip::k_abc_chunks.
+// rows over one term array) with the packed-dictionary encoding of csrc/poly.hip::k_abc_chunks.
 struct ZkeyHost {
   uint32_t nVars = 0, nPub = 0, dom = 0;
   int logn = 0;
@@ -86,6 +86,8 @@ int wprog_signals(const uint8_t* img, size_t len, std::vector<WSignal>& out, std
 int inputs_from_json(const std::vector<WSignal>& sigs, const char* json, std::vector<uint32_t>& out,
                      std::string& err);
 
+// range checks of 8-limb little-endian values: v < r (scalar field), v < q (base field)
 bool fr_lt_r(const uint32_t v[8]);
+bool fq_lt_q(const uint32_t v[8]);
 
 }  // namespace zkfl

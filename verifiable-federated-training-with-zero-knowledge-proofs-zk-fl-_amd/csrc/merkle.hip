@@ -227,7 +227,7 @@ hipError_t launch_rows(const PosConsts& K, size_t n, const Fr* in, size_t in_str
   return hipGetLastError();
 }
 
-hipError_t rows_any(const PosConsts* W, uint32_t arity, size_t n, const Fr* in, size_t in_stride, bool in_mont,
+hipError_t rows_of_arity(const PosConsts* W, uint32_t arity, size_t n, const Fr* in, size_t in_stride, bool in_mont,
                     Fr* out, size_t out_stride, bool out_mont, hipStream_t st) {
   const PosConsts& K = W[arity + 1];
   switch (arity + 1) {
@@ -353,19 +353,19 @@ hipError_t fr_to_mont_batch(const Fr* in, size_t n, Fr* out, hipStream_t st) {
 
 hipError_t poseidon_batch(const PosTables* P, uint32_t arity, size_t n, const Fr* in, Fr* out, hipStream_t st) {
   if (arity < 1 || arity > POS_MAX_ARITY) return hipErrorInvalidValue;
-  return rows_any(P->w, arity, n, in, arity, false, out, 1, false, st);
+  return rows_of_arity(P->w, arity, n, in, arity, false, out, 1, false, st);
 }
 
 hipError_t vector_hash_batch(const PosTables* P, uint32_t len, size_t n, const Fr* in, Fr* out, bool out_mont,
                              Fr* scratch, hipStream_t st) {
   if (len < 1 || len > VHASH_CHUNK * VHASH_CHUNK) return hipErrorInvalidValue;
-  if (len <= VHASH_CHUNK) return rows_any(P->w, len, n, in, len, false, out, 1, out_mont, st);
+  if (len <= VHASH_CHUNK) return rows_of_arity(P->w, len, n, in, len, false, out, 1, out_mont, st);
   const uint32_t nch = (len + VHASH_CHUNK - 1) / VHASH_CHUNK;
   for (uint32_t c = 0; c < nch; c++) {
     const uint32_t cl = std::min(VHASH_CHUNK, len - c * VHASH_CHUNK);
-    ZK_CHECK(rows_any(P->w, cl, n, in + (size_t)c * VHASH_CHUNK, len, false, scratch + c, nch, true, st));
+    ZK_CHECK(rows_of_arity(P->w, cl, n, in + (size_t)c * VHASH_CHUNK, len, false, scratch + c, nch, true, st));
   }
-  return rows_any(P->w, nch, n, scratch, nch, true, out, 1, out_mont, st);
+  return rows_of_arity(P->w, nch, n, scratch, nch, true, out, 1, out_mont, st);
 }
 
 size_t merkle_work_size(size_t n, uint32_t depth) {

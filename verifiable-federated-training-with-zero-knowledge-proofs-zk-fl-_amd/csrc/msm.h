@@ -1288,7 +1288,7 @@ hipError_t msm_sort(const MsmBases<F>& b, MsmScratch<F>& pl, uint32_t* nnz, cons
 // scalars and base index map (B1's sort serves B2: msm_sort once, accumulate on both curves).
 template <class F>
 hipError_t msm_accumulate_sorted(const MsmBases<F>& b, const uint16_t* keys, const uint32_t* vals, MsmTail<F>& t,
-                                 hipStream_t st, Profiler* prof = nullptr, const char* tag = nullptr) {
+                                 hipStream_t st, Profiler* prof, const char* tag) {
   if (b.n == 0) return hipSuccess;
   if (b.c != t.c) return hipErrorInvalidValue;
   const size_t m = b.n * msm_w_of(b.c);
@@ -1350,8 +1350,7 @@ hipError_t msm_accumulate_sorted_multi(const MsmBases<F>* const* b, const uint16
 // infinity.
 template <class F>
 hipError_t msm_accumulate(const MsmBases<F>& b, MsmScratch<F>& pl, MsmTail<F>& t, const uint32_t* d_scalars,
-                          const uint32_t* d_extra, hipStream_t st, Profiler* prof = nullptr,
-                          const char* tag = nullptr) {
+                          const uint32_t* d_extra, hipStream_t st, Profiler* prof, const char* tag) {
   ZK_CHECK(msm_sort(b, pl, t.nnz, d_scalars, d_extra, st));
   return msm_accumulate_sorted(b, pl.keys_out, pl.vals_out, t, st, prof, tag);
 }
@@ -1412,7 +1411,7 @@ hipError_t msm_wsum(const MsmTailArgs<F>& ta, int n, hipStream_t st, bool fast) 
 }
 
 template <class F>
-hipError_t msm_tails(MsmTail<F>* const* t, XYZZ<F>* const* outs, int n, hipStream_t st, bool fast = false) {
+hipError_t msm_tails(MsmTail<F>* const* t, XYZZ<F>* const* outs, int n, hipStream_t st, bool fast) {
   ZK_CHECK(msm_stitch(t, n, st));
   return msm_wsum(msm_tail_args<F>(t, outs, n), n, st, fast);
 }
@@ -1477,59 +1476,11 @@ hipError_t msm_tails_joint(MsmTail<S1>* const* t1, XYZZ<S1>* const* o1, int n1, 
 
 template <class F>
 hipError_t msm_run(const MsmBases<F>& b, MsmScratch<F>& pl, MsmTail<F>& t, const uint32_t* d_scalars,
-                   const uint32_t* d_extra, XYZZ<F>* d_out, hipStream_t st, Profiler* prof = nullptr,
-                   const char* tag = nullptr) {
+                   const uint32_t* d_extra, XYZZ<F>* d_out, hipStream_t st, Profiler* prof, const char* tag) {
   MsmTail<F>* tp = &t;
   ZK_CHECK(msm_tails_reset(&tp, 1, st));
   ZK_CHECK(msm_accumulate(b, pl, t, d_scalars, d_extra, st, prof, tag));
   return msm_tails(&tp, &d_out, 1, st);
 }
-
-// Non-template entry points (one translation unit per curve: msm_g1.hip / msm_g2.hip).
-#define ZKFL_MSM_DEFINE(SUF, F)                                                                          \
-  hipError_t zk_wtrace_bind_##SUF(const WtBuf& b) { return zk_wtrace_bind_tu(b); }                      \
-  hipError_t msm_bases_alloc_##SUF(MsmBases<F>& b, size_t n, int c) { return msm_bases_alloc(b, n, c); } \
-  hipError_t msm_bases_set_##SUF(MsmBases<F>& b, const Affine<F>* src, const uint32_t* h_sidx,          \
-                                 uint32_t extra_start, hipStream_t st) {                                 \
-    return msm_bases_set(b, src, h_sidx, extra_start, st);                                               \
-  }                                                                                                      \
-  void msm_bases_free_##SUF(MsmBases<F>& b) { msm_bases_free(b); }                                       \
-  hipError_t msm_scratch_alloc_##SUF(MsmScratch<F>& s, size_t cap, int c, hipStream_t st) {              \
-    return msm_scratch_alloc(s, cap, c, st);                                                             \
-  }                                                                                                      \
-  void msm_scratch_free_##SUF(MsmScratch<F>& s) { msm_scratch_free(s); }                                 \
-  hipError_t msm_tail_alloc_##SUF(MsmTail<F>& t, size_t cap, int c) { return msm_tail_alloc(t, cap, c); } \
-  void msm_tail_free_##SUF(MsmTail<F>& t) { msm_tail_free(t); }                                          \
-  hipError_t msm_accumulate_##SUF(const MsmBases<F>& b, MsmScratch<F>& s, MsmTail<F>& t, const uint32_t* sc, \
-                                  const uint32_t* ex, hipStream_t st, Profiler* prof, const char* tag) { \
-    return msm_accumulate(b, s, t, sc, ex, st, prof, tag);                                               \
-  }                                                                                                      \
-  hipError_t msm_sort_##SUF(const MsmBases<F>& b, MsmScratch<F>& s, uint32_t* nnz, const uint32_t* sc,      \
-                            const uint32_t* ex, hipStream_t st) {                                        \
-    return msm_sort(b, s, nnz, sc, ex, st);                                                              \
-  }                                                                                                      \
-  hipError_t msm_accumulate_sorted_##SUF(const MsmBases<F>& b, const uint16_t* keys, const uint32_t* vals,  \
-                                         MsmTail<F>& t, hipStream_t st, Profiler* prof, const char* tag) { \
-    return msm_accumulate_sorted(b, keys, vals, t, st, prof, tag);                                       \
-  }                                                                                                      \
-  hipError_t msm_sort_multi_##SUF(const MsmBases<F>* const* b, MsmScratch<F>* const* s, uint32_t* const* nnz, \
-                                  const uint32_t* const* sc, const uint32_t* const* ex, int n, hipStream_t st) { \
-    return msm_sort_multi(b, s, nnz, sc, ex, n, st);                                                     \
-  }                                                                                                      \
-  hipError_t msm_accumulate_sorted_multi_##SUF(const MsmBases<F>* const* b, const uint16_t* const* keys,      \
-                                               const uint32_t* const* vals, MsmTail<F>* const* t, int n,  \
-                                               hipStream_t st) {                                          \
-    return msm_accumulate_sorted_multi(b, keys, vals, t, n, st);                                         \
-  }                                                                                                      \
-  hipError_t msm_tails_##SUF(MsmTail<F>* const* t, XYZZ<F>* const* outs, int n, hipStream_t st, bool fast) { \
-    return msm_tails(t, outs, n, st, fast);                                                              \
-  }                                                                                                      \
-  hipError_t msm_tails_reset_##SUF(MsmTail<F>* const* t, int n, hipStream_t st) {                        \
-    return msm_tails_reset(t, n, st);                                                                    \
-  }                                                                                                      \
-  hipError_t msm_run_##SUF(const MsmBases<F>& b, MsmScratch<F>& s, MsmTail<F>& t, const uint32_t* sc,     \
-                           const uint32_t* ex, XYZZ<F>* out, hipStream_t st, Profiler* prof, const char* tag) { \
-    return msm_run(b, s, t, sc, ex, out, st, prof, tag);                                                 \
-  }
 
 }  // namespace zkfl

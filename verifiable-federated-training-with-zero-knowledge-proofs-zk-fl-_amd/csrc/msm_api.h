@@ -1,4 +1,4 @@
-// MSM plan object and non-template entry points (see msm.h for the algorithm).
+// MSM plan objects and the engine's entry points (see msm.h for the algorithm).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -181,40 +181,77 @@ inline int msm_pick_c(size_t n) {
 constexpr int MSM_TAIL_MAX = 4;  // MSM tails per batched launch (the 4 G1 MSMs of a proof)
 constexpr int MSM_TAIL_RED = 4 * MSM_RB;  // reduction block outputs per bucket set (<= 2 level-1 blocks of 128 lanes)
 
-#define ZKFL_MSM_DECLARE(SUF, F)                                                                    \
-  hipError_t msm_bases_alloc_##SUF(MsmBases<F>& b, size_t n, int c);                                \
-  hipError_t msm_bases_set_##SUF(MsmBases<F>& b, const Affine<F>* src, const uint32_t* h_sidx,      \
-                                 uint32_t extra_start, hipStream_t st);                              \
-  void msm_bases_free_##SUF(MsmBases<F>& b);                                                        \
-  hipError_t msm_scratch_alloc_##SUF(MsmScratch<F>& s, size_t cap, int c, hipStream_t st);          \
-  void msm_scratch_free_##SUF(MsmScratch<F>& s);                                                    \
-  hipError_t msm_tail_alloc_##SUF(MsmTail<F>& t, size_t cap, int c);                                \
-  void msm_tail_free_##SUF(MsmTail<F>& t);                                                          \
-  /* digits -> sort -> accumulation into t (the MSM is finished by msm_tails) */                    \
-  hipError_t msm_accumulate_##SUF(const MsmBases<F>& b, MsmScratch<F>& s, MsmTail<F>& t,            \
-                                  const uint32_t* scalars, const uint32_t* extra, hipStream_t st,    \
-                                  Profiler* prof, const char* tag);                                  \
-  /* empty buckets + zero nnz of n <= MSM_TAIL_MAX tails (before their accumulations) */              \
-  hipError_t msm_tails_reset_##SUF(MsmTail<F>* const* t, int n, hipStream_t st);                     \
-  hipError_t msm_sort_##SUF(const MsmBases<F>& b, MsmScratch<F>& s, uint32_t* nnz, const uint32_t* sc,  \
-                            const uint32_t* ex, hipStream_t st);                                        \
-  hipError_t msm_accumulate_sorted_##SUF(const MsmBases<F>& b, const uint16_t* keys, const uint32_t* vals, \
-                                         MsmTail<F>& t, hipStream_t st, Profiler* prof, const char* tag);  \
-  /* stitching + bucket reduction of n <= MSM_TAIL_MAX accumulated MSMs -> outs[i] (device) */      \
-  hipError_t msm_tails_##SUF(MsmTail<F>* const* t, XYZZ<F>* const* outs, int n, hipStream_t st,     \
-                             bool fast = false);                                                      \
-  hipError_t msm_run_##SUF(const MsmBases<F>& b, MsmScratch<F>& s, MsmTail<F>& t, const uint32_t* scalars, \
-                           const uint32_t* extra, XYZZ<F>* out, hipStream_t st, Profiler* prof, const char* tag); \
-  /* n <= MSM_TAIL_MAX independent MSMs of one window width: their sorts in the same four launches, */   \
-  /* their accumulations in one launch (blockIdx.y = MSM) */                                             \
-  hipError_t msm_sort_multi_##SUF(const MsmBases<F>* const* b, MsmScratch<F>* const* s, uint32_t* const* nnz, \
-                                  const uint32_t* const* sc, const uint32_t* const* ex, int n, hipStream_t st); \
-  hipError_t msm_accumulate_sorted_multi_##SUF(const MsmBases<F>* const* b, const uint16_t* const* keys,      \
-                                               const uint32_t* const* vals, MsmTail<F>* const* t, int n,  \
-                                               hipStream_t st);
+// The engine's entry points, templates over the curve (F = FqOps: G1, Fq2Ops: G2).  msm.h defines
+// them; msm_g1.hip and msm_g2.hip hold the two instantiations (ZKFL_MSM_API), every other unit
+// links against those.
+template <class F>
+hipError_t msm_bases_alloc(MsmBases<F>& b, size_t n, int c);
+template <class F>
+hipError_t msm_bases_set(MsmBases<F>& b, const Affine<F>* src, const uint32_t* h_sidx, uint32_t extra_start,
+                         hipStream_t st);
+template <class F>
+void msm_bases_free(MsmBases<F>& b);
+template <class F>
+hipError_t msm_scratch_alloc(MsmScratch<F>& s, size_t cap, int c, hipStream_t st);
+template <class F>
+void msm_scratch_free(MsmScratch<F>& s);
+template <class F>
+hipError_t msm_tail_alloc(MsmTail<F>& t, size_t cap, int c);
+template <class F>
+void msm_tail_free(MsmTail<F>& t);
+// digits -> sort -> accumulation into t (the MSM is finished by msm_tails)
+template <class F>
+hipError_t msm_accumulate(const MsmBases<F>& b, MsmScratch<F>& s, MsmTail<F>& t, const uint32_t* scalars,
+                          const uint32_t* extra, hipStream_t st, Profiler* prof, const char* tag);
+// empty buckets + zero nnz of n <= MSM_TAIL_MAX tails (before their accumulations)
+template <class F>
+hipError_t msm_tails_reset(MsmTail<F>* const* t, int n, hipStream_t st);
+template <class F>
+hipError_t msm_sort(const MsmBases<F>& b, MsmScratch<F>& s, uint32_t* nnz, const uint32_t* sc, const uint32_t* ex,
+                    hipStream_t st);
+template <class F>
+hipError_t msm_accumulate_sorted(const MsmBases<F>& b, const uint16_t* keys, const uint32_t* vals, MsmTail<F>& t,
+                                 hipStream_t st, Profiler* prof, const char* tag);
+// stitching + bucket reduction of n <= MSM_TAIL_MAX accumulated MSMs -> outs[i] (device)
+template <class F>
+hipError_t msm_tails(MsmTail<F>* const* t, XYZZ<F>* const* outs, int n, hipStream_t st, bool fast = false);
+template <class F>
+hipError_t msm_run(const MsmBases<F>& b, MsmScratch<F>& s, MsmTail<F>& t, const uint32_t* scalars,
+                   const uint32_t* extra, XYZZ<F>* out, hipStream_t st, Profiler* prof, const char* tag);
+// n <= MSM_TAIL_MAX independent MSMs of one window width: their sorts in the same four launches,
+// their accumulations in one launch (blockIdx.y = MSM)
+template <class F>
+hipError_t msm_sort_multi(const MsmBases<F>* const* b, MsmScratch<F>* const* s, uint32_t* const* nnz,
+                          const uint32_t* const* sc, const uint32_t* const* ex, int n, hipStream_t st);
+template <class F>
+hipError_t msm_accumulate_sorted_multi(const MsmBases<F>* const* b, const uint16_t* const* keys,
+                                       const uint32_t* const* vals, MsmTail<F>* const* t, int n, hipStream_t st);
 
-ZKFL_MSM_DECLARE(g1, FqOps)
-ZKFL_MSM_DECLARE(g2, Fq2Ops)
+// The entry points above for one curve: X = `extern template` here, `template` in the curve's unit.
+#define ZKFL_MSM_API(X, F)                                                                                     \
+  X hipError_t msm_bases_alloc<F>(MsmBases<F>&, size_t, int);                                                  \
+  X hipError_t msm_bases_set<F>(MsmBases<F>&, const Affine<F>*, const uint32_t*, uint32_t, hipStream_t);       \
+  X void msm_bases_free<F>(MsmBases<F>&);                                                                      \
+  X hipError_t msm_scratch_alloc<F>(MsmScratch<F>&, size_t, int, hipStream_t);                                 \
+  X void msm_scratch_free<F>(MsmScratch<F>&);                                                                  \
+  X hipError_t msm_tail_alloc<F>(MsmTail<F>&, size_t, int);                                                    \
+  X void msm_tail_free<F>(MsmTail<F>&);                                                                        \
+  X hipError_t msm_accumulate<F>(const MsmBases<F>&, MsmScratch<F>&, MsmTail<F>&, const uint32_t*,             \
+                                 const uint32_t*, hipStream_t, Profiler*, const char*);                        \
+  X hipError_t msm_tails_reset<F>(MsmTail<F>* const*, int, hipStream_t);                                       \
+  X hipError_t msm_sort<F>(const MsmBases<F>&, MsmScratch<F>&, uint32_t*, const uint32_t*, const uint32_t*,    \
+                           hipStream_t);                                                                       \
+  X hipError_t msm_accumulate_sorted<F>(const MsmBases<F>&, const uint16_t*, const uint32_t*, MsmTail<F>&,     \
+                                        hipStream_t, Profiler*, const char*);                                  \
+  X hipError_t msm_tails<F>(MsmTail<F>* const*, XYZZ<F>* const*, int, hipStream_t, bool);                      \
+  X hipError_t msm_run<F>(const MsmBases<F>&, MsmScratch<F>&, MsmTail<F>&, const uint32_t*, const uint32_t*,   \
+                          XYZZ<F>*, hipStream_t, Profiler*, const char*);                                      \
+  X hipError_t msm_sort_multi<F>(const MsmBases<F>* const*, MsmScratch<F>* const*, uint32_t* const*,           \
+                                 const uint32_t* const*, const uint32_t* const*, int, hipStream_t);            \
+  X hipError_t msm_accumulate_sorted_multi<F>(const MsmBases<F>* const*, const uint16_t* const*,               \
+                                              const uint32_t* const*, MsmTail<F>* const*, int, hipStream_t);
+ZKFL_MSM_API(extern template, FqOps)
+ZKFL_MSM_API(extern template, Fq2Ops)
 
 // The G1 tails and the G2 tail of one proof as ONE launch sequence (msm_joint.hip): stitching and
 // reduction of both curves side by side, blockIdx.y over all n1 + n2 MSMs

@@ -2,5 +2,6 @@
 #include "msm.h"
 
 namespace zkfl {
-ZKFL_MSM_DEFINE(g1, FqOps)
+hipError_t zk_wtrace_bind_g1(const WtBuf& b) { return zk_wtrace_bind_tu(b); }
+ZKFL_MSM_API(template, FqOps)
 }  // namespace zkfl

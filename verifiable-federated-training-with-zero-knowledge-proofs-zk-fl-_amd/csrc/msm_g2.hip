@@ -2,5 +2,6 @@
 #include "msm.h"
 
 namespace zkfl {
-ZKFL_MSM_DEFINE(g2, Fq2Ops)
+hipError_t zk_wtrace_bind_g2(const WtBuf& b) { return zk_wtrace_bind_tu(b); }
+ZKFL_MSM_API(template, Fq2Ops)
 }  // namespace zkfl

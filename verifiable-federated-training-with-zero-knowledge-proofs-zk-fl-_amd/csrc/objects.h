@@ -1,0 +1,162 @@
+// The C ABI's objects (the opaque handles of include/zkfl.h) and what the library's units share
+// around them: error reporting, the context's reference count, and what the scheduler
+// (csrc/prove.hip) exposes to the key loader (csrc/key_load.hip).  Internal to the library.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <atomic>
+#include <string>
+#include <vector>
+
+#include "curve.h"
+#include "field.h"
+#include "msm_api.h"
+#include "ntt.h"
+#include "prof.h"
+#include "wtrace.h"
+#include "zkfl.h"
+
+namespace zkfl {
+struct VkDev;      // verify.h
+struct PosTables;  // merkle.h
+struct WProg;      // witness.h
+
+// Set the calling thread's error string (zkfl_last_error; one definition, csrc/zkfl.hip) and
+// return the code.
+int fail(int code, const std::string& msg);
+int hip_fail(hipError_t e, const char* where);
+}  // namespace zkfl
+
+#define HIP_TRY(x, where)                              \
+  do {                                                 \
+    hipError_t _e = (x);                               \
+    if (_e != hipSuccess) return ::zkfl::hip_fail(_e, where); \
+  } while (0)
+
+// The handle types are global names of the C ABI; what they hold lives in namespace zkfl (every
+// unit that includes this header is one of the library's own and uses that namespace).
+using namespace zkfl;
+
+struct WitPipe;  // csrc/prove.hip
+
+struct zkfl_ctx {
+  int device = 0;
+  hipStream_t st = nullptr;  // primitives, key loading, verification
+  Profiler prof;
+  zkfl::VkDev* vk = nullptr;       // last prepared verification key (reused while the vk bytes repeat)
+  zkfl::PosTables* pos = nullptr;  // Poseidon constants of every width (first hashing call)
+  void* asm_buf = nullptr;   // zkfl_groth16_assemble's device buffers (grown on demand, reused)
+  size_t asm_cap = 0;
+  WtBuf wt;                  // wave-timeline records (ZK_WTRACE builds, zkfl_debug_wtrace)
+  // Lifetime: the caller's handle holds one reference and every key and witness program made on
+  // the context holds one more, so zkfl_ctx_destroy and the children's frees may come in any
+  // order (the N-API finalizers run in an unspecified order); the device state goes with the last.
+  std::atomic<int> refs{1};
+};
+
+// One in-flight proof: its own stream, scratch and per-proof vectors.
+struct ProofSlot {
+  hipStream_t st_main = nullptr;
+  hipEvent_t ev_done = nullptr;
+  MsmScratch<FqOps> g1s;   // digit/sort scratch shared by the four G1 MSMs
+#if ZK_KNOCKOUT & 2
+  MsmScratch<FqOps> g1s_ko[3];  // sort knock-out (timing only): A, B, C+H keep their first sort
+#endif
+  MsmTail<FqOps> g1t[4];   // A, B1, C, H: accumulated, finished by one batched tail
+  MsmScratch<Fq2Ops> g2s;
+  MsmTail<Fq2Ops> g2t;
+  Fr* extra = nullptr;  // [4] blinding scalars 1, r, s, -rs (= h + n: the extra slots follow h)
+  Fr* abc = nullptr;  // [3n]
+  Fr* abc_head = nullptr;  // [ceil(K / ABC_L)] ABC segmented-sum partials
+  Fr* abc_tail = nullptr;
+  Fr* h = nullptr;    // [n]
+  G1P* res = nullptr;     // [5]: A', B1', C', H, T
+  G2P* resB2 = nullptr;   // [1]
+  Fr* d_rs = nullptr;     // r, s (64 B) | GLV halves s1, s2, r1, r2 (4 x 32 B)
+  uint32_t* d_parts = nullptr;  // [96]: this rank's part of a split proof (A'|B1'|B2'|C'|H, std affine)
+  uint8_t* pinned = nullptr;    // proof (256) | r, s (64) | GLV halves (128) | witness address (8, at
+                                // W_PTR_OFF) | pad | part (768 at 512)
+  // the low-latency schedule (enqueue_proof_lowlat, one proof alone): two side streams, their
+  // events (B sorted and B1 accumulated | B2 final | T = s pi_A + r B1 final) and B's own sort
+  // scratch, so C + H can sort on the main stream while B2 still reads B's pairs; made on first use
+  hipStream_t st_lat[2] = {nullptr, nullptr};
+  hipEvent_t ev_lat[3] = {nullptr, nullptr, nullptr};
+  MsmScratch<FqOps> g1s_b;
+  MsmScratch<FqOps> g1s_a;  // A's sort scratch in the overlapped schedule (A beside C + H)
+  // graph replay (default on; ZKFL_GRAPH=0 off): the one-stream proof chain captured once per witness address
+  struct Graph {
+    const Fr* w = nullptr;
+    hipGraph_t g = nullptr;
+    hipGraphExec_t ex = nullptr;
+  };
+  std::vector<Graph> graphs;
+  // the graph's witness: each graph-replayed proof first copies its witness here (nVars x 32 B,
+  // a few us of HBM time), so one graph per slot serves every witness buffer
+  Fr* w_stage = nullptr;
+  uint32_t direct_proofs = 0;     // proofs this slot ran kernel by kernel (the first one: no capture)
+  // B2 shares B1's digit sort, so its tail counts with B1's nnz (g2t.nnz == g1t[1].nnz, owned
+  // by g1t[1]): no copy between them
+  bool nnz_alias = false;
+  bool busy = false;
+  int index = 0;                  // position among its key's slots
+  size_t job = 0;                 // index of the in-flight proof in its batch
+  uint8_t* out_proof = nullptr;   // where its 256 proof bytes go (nullable)
+  uint8_t* out_part = nullptr;    // split proofs: where the 768 part bytes go (nullable)
+};
+
+struct zkfl_key {
+  zkfl_ctx* ctx = nullptr;
+  uint32_t nVars = 0, nPub = 0, n = 0;
+  int logn = 0;
+  size_t nC = 0;  // C query length
+  size_t K = 0;
+  uint32_t* rows = nullptr;  // [2n+1]: A rows then B rows over one term array
+  uint32_t* cols = nullptr;  // [K]
+  Fr* coefs = nullptr;       // [K] (wide) or the coefficient dictionary (packed)
+  uint32_t cshift = 0;       // packed terms: col | dict index << cshift in cols[]; 0 = wide
+  MsmBases<FqOps> bA, bB1;
+  MsmBases<Fq2Ops> bB2;
+  // C and H as ONE MSM: pi_C only needs their sum, so one sort and one tail serve both queries.
+  // Bases: C's (scalars: the private wires) then H's (scalars: h, addressed through the extra
+  // pointer = the slot's h vector, whose extra slots 1, r, s, -rs follow it).
+  MsmBases<FqOps> bCH;
+  // the parity hook's zeros (zkfl_debug_prove_parts, first call, which returns C and H apart): it
+  // runs the C + H MSM twice, once with a zero h (C alone) and once with a zero witness (H alone),
+  // so the key holds no separate C and H bases (they were ~0.5 GB of expanded bases per key at 2^18)
+  Fr* dbg_zero = nullptr;
+  bool share_b = false;  // B1 and B2 have the same base index map: one digit sort serves both
+  // small keys (domain <= 2^16, config 5's circuits): a proof sorts A, B1 and C + H in the same four
+  // launches and accumulates them in one (msm_sort_multi / msm_accumulate_sorted_multi), after ABC /
+  // NTT; the slots hold A's and B's sort scratch for it (g1s_a, g1s_b)
+  bool front = false;
+  int msm_c = MSM_C;     // window bits of every base set of the key (msm_pick_c of its largest)
+  NttPlan ntt;
+  std::vector<ProofSlot*> slots;
+  int max_slots = 3;
+  // Split proofs (zkfl_zkey_load_shard): this key holds base i of every query only when
+  // i % nshards == shard, and the alpha/beta/delta augmentation bases only on shard 0, so its
+  // MSMs are this shard's share of each proof's sums.
+  uint32_t shard = 0, nshards = 1;
+  WitPipe* wpipe = nullptr;  // batched witnesses of the single-key full-prove entry points
+};
+
+struct zkfl_witness {
+  const zkfl_key* key = nullptr;
+  Fr* d = nullptr;  // nVars std-form elements
+  std::vector<uint8_t> pub;  // nPub x 32 B
+};
+
+struct zkfl_wprog {
+  zkfl_ctx* ctx = nullptr;
+  zkfl::WProg* p = nullptr;
+};
+
+namespace zkfl {
+void ctx_retain(zkfl_ctx* ctx);
+void ctx_release(zkfl_ctx* ctx);  // drops one reference; the last one tears the context down
+// csrc/prove.hip: the key's idx-th slot (idx % max_slots), made on first use; all of its slots and
+// its witness pipe released (key_release, csrc/key_load.hip)
+int get_slot(zkfl_key* k, size_t idx, ProofSlot** out);
+void key_release_slots(zkfl_key* k);
+}  // namespace zkfl

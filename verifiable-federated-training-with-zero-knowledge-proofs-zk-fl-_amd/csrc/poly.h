@@ -1,0 +1,55 @@
+// The polynomial stage of a proof (csrc/poly.hip): a, b, c on the domain from the QAP's CSR rows
+// (k_abc_chunks, k_abc_rows), h = a b - c on the coset (k_join; the coset NTT between them is
+// ntt.h's), and the proof chain's first kernel (k_proof_start).  Each function below only launches
+// its kernel on st; the scheduler (csrc/prove.hip) keeps the sequencing and the error checks.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "field.h"
+#include "glv.h"
+
+namespace zkfl {
+
+// terms per lane of k_abc_chunks (the slot's head / tail partials hold one element per chunk)
+constexpr uint32_t ABC_L = 16;
+
+// Terms are either packed (col | coefficient-dictionary index << cshift in one u32: circuits
+// with few distinct coefficients, e.g. 1,971 among the 7.0 M A/B terms of the training circuit;
+// 4 B per term instead of 36 B, the dictionary stays in cache) or wide (cols[] + coefs[]).
+struct AbcTerms {
+  const uint32_t* cols;  // packed terms, or column indices (wide)
+  const Fr* coefs;       // dictionary (packed) or one coefficient per term (wide)
+  uint32_t cshift;       // 0: wide
+};
+
+// The tails a proof chain empties at its start (k_proof_start): up to 4 G1 and 1 G2, each as
+// its bucket array (16-B vectors), nnz counter and liveness flags.
+struct ProofStart {
+  uint4* buckets[5];
+  uint32_t nvec[5];
+  uint32_t* nnz[5];
+  uint32_t* live[5];
+  int n;
+  // graph replay: the proof's witness, copied into the slot's stage (w_dst, w_nvec 16-B vectors)
+  // from the device address the host left in the pinned buffer (w_src_host); w_dst null: none
+  const uint64_t* w_src_host;
+  uint4* w_dst;
+  uint32_t w_nvec;
+};
+
+// words of the slot's pinned r | s | GLV halves, copied to the device by k_proof_start
+constexpr int RS_WORDS = (64 + 4 * (int)sizeof(GlvScalar)) / 4;
+
+// k_abc_chunks over the K terms (packed when T.cshift != 0), K > 0
+void abc_chunks(hipStream_t st, const uint32_t* rp, uint32_t nrows, const AbcTerms& T, const Fr* w, uint32_t K,
+                Fr* head, Fr* tail, Fr* abc);
+void abc_rows(hipStream_t st, const uint32_t* rp, size_t n, uint32_t K, const Fr* head, const Fr* tail, Fr* abc);
+void join_h(hipStream_t st, const Fr* abc, size_t n, Fr* h);
+void proof_start(hipStream_t st, const uint32_t* rs_host, uint32_t* d_rs, Fr* extra, int plain, uint32_t* res3,
+                 const ProofStart& ps);
+// in place, n elements (zkfl_ntt_coset's conversions around the transform)
+void fr_std_to_mont(hipStream_t st, Fr* a, size_t n);
+void fr_mont_to_std(hipStream_t st, Fr* a, size_t n);
+
+}  // namespace zkfl

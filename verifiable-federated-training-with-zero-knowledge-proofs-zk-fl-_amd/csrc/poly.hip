@@ -1,0 +1,224 @@
+// The polynomial stage's kernels (see poly.h).
+#include "poly.h"
+
+#include "common.h"
+#include "msm_api.h"
+#include "wtrace.h"
+
+using namespace zkfl;
+
+namespace {
+
+// ABC as a segmented sum over the flat term array (A rows then B rows; rp[0..2n] row pointers).
+// coef raw = coef * R^2 mod r (snarkjs zkey section 4), w std form, so
+// mont_mul(coef_raw, w) = coef * w * R = Montgomery form of coef*w.  Rows range from 1 to ~130
+// terms (Poseidon S-box inputs carry ~61-term combinations), so one lane per row leaves ~2/3 of
+// the lanes idle; instead lane c takes the ABC_L terms [c*L, c*L+L), emitting the sum of its
+// first row segment to head[c], of its last to tail[c], and rows wholly inside the chunk
+// straight to abc[row]; k_abc_rows stitches rows j and n+j and forms c = a*b.
+// (ABC_L and the term encodings, AbcTerms: poly.h)
+template <bool PACKED>
+__global__ void __launch_bounds__(64) k_abc_chunks(const uint32_t* __restrict__ rp, uint32_t nrows, AbcTerms T,
+                                                   const Fr* __restrict__ w, uint32_t K, Fr* __restrict__ head,
+                                                   Fr* __restrict__ tail, Fr* __restrict__ abc) {
+  ZK_WT(WT_ABC);
+  ZK_LIGHT();
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t p0 = c * ABC_L;
+  if (p0 >= K) return;
+  const uint32_t p1 = p0 + ABC_L < K ? p0 + ABC_L : K;
+  const uint32_t* __restrict__ cols = T.cols;
+  const Fr* __restrict__ coefs = T.coefs;
+  const uint32_t cmask = PACKED ? (1u << T.cshift) - 1u : 0xFFFFFFFFu;
+  auto coef_of = [&](uint32_t t, uint32_t p) { return PACKED ? coefs[t >> T.cshift] : coefs[p]; };
+  // row containing p0: largest r with rp[r] <= p0 (empty rows share their start with the next)
+  auto row_of = [&](uint32_t p, uint32_t lo) {
+    uint32_t hi = nrows - 1;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi + 1) >> 1;
+      if (rp[mid] <= p) lo = mid;
+      else hi = mid - 1;
+    }
+    return lo;
+  };
+  uint32_t r = row_of(p0, 0), rend = rp[r + 1];
+  Fr acc = fp_zero<FrP>();
+  bool first = true;
+  // software-pipelined: term p+1's witness gather (and p+2's term word) are in flight while
+  // term p is multiplied
+  uint32_t t1 = (p0 + 1 < p1) ? cols[p0 + 1] : 0u;
+  const uint32_t t0 = cols[p0];
+  Fr wv = w[t0 & cmask], cf = coef_of(t0, p0);
+  for (uint32_t p = p0; p < p1; p++) {
+    Fr wn, cn;
+    uint32_t t2 = 0;
+    if (p + 1 < p1) {
+      wn = w[t1 & cmask];
+      cn = coef_of(t1, p + 1);
+    }
+    if (p + 2 < p1) t2 = cols[p + 2];
+    if (p == rend) {  // row boundary inside the chunk
+      if (first) head[c] = acc;
+      else abc[r] = acc;
+      first = false;
+      acc = fp_zero<FrP>();
+      // next non-empty row: usually r + 1; a run of empty rows (the domain padding after the
+      // last constraint: ~241 K rows at 2^19) is skipped by binary search, not walked row by row
+      r++;
+      rend = rp[r + 1];
+      if (rend == p) {
+        r = row_of(p, r);
+        rend = rp[r + 1];
+      }
+    }
+    acc = fp_add(acc, fp_mul(cf, wv));
+    wv = wn;
+    cf = cn;
+    t1 = t2;
+  }
+  if (first) head[c] = acc;
+  else tail[c] = acc;
+}
+
+__device__ __forceinline__ Fr abc_row(const uint32_t* __restrict__ rp, uint32_t r, uint32_t K,
+                                      const Fr* __restrict__ head, const Fr* __restrict__ tail,
+                                      const Fr* __restrict__ abc) {
+  const uint32_t s = rp[r], e = rp[r + 1];
+  if (s == e) return fp_zero<FrP>();
+  const uint32_t c0 = s / ABC_L, c1 = (e - 1) / ABC_L;
+  const bool starts = (s == c0 * ABC_L);
+  if (c0 == c1) {
+    const uint32_t cend = (c0 + 1) * ABC_L < K ? (c0 + 1) * ABC_L : K;
+    if (starts) return head[c0];
+    if (e == cend) return tail[c0];
+    return abc[r];  // wholly inside the chunk: written by k_abc_chunks
+  }
+  Fr acc = starts ? head[c0] : tail[c0];
+  for (uint32_t c = c0 + 1; c <= c1; c++) acc = fp_add(acc, head[c]);
+  return acc;
+}
+
+__global__ void __launch_bounds__(256) k_abc_rows(const uint32_t* __restrict__ rp, size_t n, uint32_t K,
+                                                  const Fr* __restrict__ head, const Fr* __restrict__ tail,
+                                                  Fr* __restrict__ abc) {
+  ZK_WT(WT_ABC_ROWS);
+  ZK_LIGHT();
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const Fr a = abc_row(rp, (uint32_t)j, K, head, tail, abc);
+  const Fr b = abc_row(rp, (uint32_t)(n + j), K, head, tail, abc);
+  abc[j] = a;
+  abc[n + j] = b;
+  abc[2 * n + j] = fp_mul(a, b);
+}
+
+// h = a*b - c (coset evaluations), to standard form for the H MSM.
+__global__ void k_join(const Fr* __restrict__ abc, size_t n, Fr* __restrict__ h) {
+  ZK_WT(WT_JOIN);
+  ZK_LIGHT();
+  size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+#if ZK_KNOCKOUT & 4
+  // NTT knock-out (timing only): a*b - c vanishes on the domain, so without the coset shift h would
+  // be zero and the H MSM would lose its digits too; a*b + c keeps h a full-size scalar vector
+  Fr v = fp_add(fp_mul(abc[j], abc[n + j]), abc[2 * n + j]);
+#else
+  Fr v = fp_sub(fp_mul(abc[j], abc[n + j]), abc[2 * n + j]);
+#endif
+  h[j] = fp_from_mont(v);
+}
+
+// Blinding scalar slots referenced by the compacted bases' index maps (std form):
+// extra = [1, r, s, -r*s].  plain -> all zero (parity hook: pure MSMs).
+// The tails the chain empties: ProofStart (poly.h).
+// A proof chain's first kernel, one launch for what were up to four: the augmentation scalars
+// (1, r, s, -rs) of the merged MSMs, res[3] = infinity (the merged C + H leaves the H slot
+// empty), and the proof's MSM tails emptied (buckets, nnz, liveness: blockIdx.y = tail).
+// rs_host: the slot's pinned r | s | GLV halves (host memory, coherent), copied to d_rs for the
+// assembly; the augmentation scalars are computed from the host copy directly.
+__global__ void __launch_bounds__(256) k_proof_start(const uint32_t* __restrict__ rs_host, uint32_t* __restrict__ d_rs,
+                                                     Fr* __restrict__ extra, int plain, uint32_t* __restrict__ res3,
+                                                     const ProofStart ps) {
+  ZK_WT(WT_SET_EXTRA);
+  ZK_LIGHT();
+  const int y = blockIdx.y;
+  if (ps.w_dst) {  // uniform per launch
+    __shared__ const uint4* src;
+    if (threadIdx.x == 0) src = reinterpret_cast<const uint4*>(*ps.w_src_host);
+    __syncthreads();
+    const size_t nb = (size_t)gridDim.x * gridDim.y * blockDim.x;
+    for (size_t i = ((size_t)y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; i < ps.w_nvec; i += nb)
+      ps.w_dst[i] = src[i];
+  }
+  if (y == 0 && blockIdx.x == 2 && threadIdx.x < RS_WORDS) d_rs[threadIdx.x] = rs_host[threadIdx.x];
+  if (y == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+    const Fr* rs = reinterpret_cast<const Fr*>(rs_host);
+    Fr one = fp_zero<FrP>();
+    one.v[0] = plain ? 0u : 1u;
+    Fr r = plain ? fp_zero<FrP>() : rs[0];
+    Fr s = plain ? fp_zero<FrP>() : rs[1];
+    extra[0] = one;
+    extra[1] = r;
+    extra[2] = s;
+    extra[3] = fp_from_mont(fp_neg(fp_mul(fp_to_mont(r), fp_to_mont(s))));
+  }
+  if (y == 0 && blockIdx.x == 1 && res3 && threadIdx.x < sizeof(G1P) / 4) res3[threadIdx.x] = 0u;  // ZZ = 0
+  if (y >= ps.n) return;
+  uint4* b = ps.buckets[y];
+  const size_t nv = ps.nvec[y];
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x)
+    b[i] = make_uint4(0, 0, 0, 0);
+  if (blockIdx.x == 0 && threadIdx.x == 0) *ps.nnz[y] = 0;
+  if (blockIdx.x == 0 && threadIdx.x < MSM_LIVE_LEVELS) ps.live[y][threadIdx.x] = 0;
+}
+
+__global__ void k_fr_std_to_mont(Fr* __restrict__ a, size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  a[i] = fp_to_mont(a[i]);
+}
+
+__global__ void k_fr_mont_to_std(Fr* __restrict__ a, size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  a[i] = fp_from_mont(a[i]);
+}
+
+}  // namespace
+
+namespace zkfl {
+
+hipError_t zk_wtrace_bind_poly(const WtBuf& b) { return zk_wtrace_bind_tu(b); }
+
+void abc_chunks(hipStream_t st, const uint32_t* rp, uint32_t nrows, const AbcTerms& T, const Fr* w, uint32_t K,
+                Fr* head, Fr* tail, Fr* abc) {
+  if (T.cshift)
+    hipLaunchKernelGGL(k_abc_chunks<true>, dim3(zk_grid((K + ABC_L - 1) / ABC_L, 64)), dim3(64), 0, st, rp, nrows, T, w,
+                       K, head, tail, abc);
+  else
+    hipLaunchKernelGGL(k_abc_chunks<false>, dim3(zk_grid((K + ABC_L - 1) / ABC_L, 64)), dim3(64), 0, st, rp, nrows, T, w,
+                       K, head, tail, abc);
+}
+
+void abc_rows(hipStream_t st, const uint32_t* rp, size_t n, uint32_t K, const Fr* head, const Fr* tail, Fr* abc) {
+  hipLaunchKernelGGL(k_abc_rows, dim3(zk_grid(n, 256)), dim3(256), 0, st, rp, n, K, head, tail, abc);
+}
+
+void join_h(hipStream_t st, const Fr* abc, size_t n, Fr* h) {
+  hipLaunchKernelGGL(k_join, dim3(zk_grid(n, 256)), dim3(256), 0, st, abc, n, h);
+}
+
+void proof_start(hipStream_t st, const uint32_t* rs_host, uint32_t* d_rs, Fr* extra, int plain, uint32_t* res3,
+                 const ProofStart& ps) {
+  hipLaunchKernelGGL(k_proof_start, dim3(128, ps.n), dim3(256), 0, st, rs_host, d_rs, extra, plain, res3, ps);
+}
+
+void fr_std_to_mont(hipStream_t st, Fr* a, size_t n) {
+  hipLaunchKernelGGL(k_fr_std_to_mont, dim3(zk_grid(n, 256)), dim3(256), 0, st, a, n);
+}
+
+void fr_mont_to_std(hipStream_t st, Fr* a, size_t n) {
+  hipLaunchKernelGGL(k_fr_mont_to_std, dim3(zk_grid(n, 256)), dim3(256), 0, st, a, n);
+}
+
+}  // namespace zkfl

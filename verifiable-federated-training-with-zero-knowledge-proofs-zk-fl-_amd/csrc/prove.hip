@@ -1,0 +1,1180 @@
+// The proof scheduler and the prove entry points: a key's proof slots (stream, scratch, MSM tails),
+// the chain a proof runs on its slot (enqueue_proof_body; enqueue_proof_lowlat for one proof alone;
+// graph replay), the batch scheduler behind every prove call (run_jobs) and the batched full-prove
+// pipe with its witness groups and JSON parse pool (full_prove_piped).  The kernels it launches
+// live in poly.hip, assemble.hip, ntt.hip and the MSM units.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <sys/random.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <cstdlib>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "assemble.h"
+#include "glv.h"
+#include "host_parse.h"
+#include "objects.h"
+#include "poly.h"
+#include "witness.h"
+
+using namespace zkfl;
+
+namespace {
+
+constexpr size_t W_PTR_OFF = 448;  // pinned: the graph-replayed proof's witness address
+
+// the proof's 256 bytes go straight into the slot's pinned buffer (k_assemble*)
+inline uint32_t* proof_out(ProofSlot* s) { return reinterpret_cast<uint32_t*>(s->pinned); }
+
+void slot_release(ProofSlot* s) {
+  if (!s) return;
+  if (s->st_main) (void)hipStreamSynchronize(s->st_main);
+  if (s->nnz_alias) s->g2t.nnz = nullptr;
+  msm_scratch_free(s->g1s);
+#if ZK_KNOCKOUT & 2
+  for (MsmScratch<FqOps>& x : s->g1s_ko) msm_scratch_free(x);
+#endif
+  for (auto& t : s->g1t) msm_tail_free(t);
+  msm_scratch_free(s->g2s);
+  msm_tail_free(s->g2t);
+  void* ptrs[] = {s->abc, s->abc_head, s->abc_tail, s->h, s->res, s->resB2, s->d_rs, s->d_parts,
+                  s->w_stage};  // extra lives in h
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  if (s->pinned) (void)hipHostFree(s->pinned);
+  for (hipStream_t st : s->st_lat)
+    if (st) (void)hipStreamSynchronize(st);
+  msm_scratch_free(s->g1s_b);
+  msm_scratch_free(s->g1s_a);
+  for (auto& gr : s->graphs) {
+    if (gr.ex) (void)hipGraphExecDestroy(gr.ex);
+    if (gr.g) (void)hipGraphDestroy(gr.g);
+  }
+  s->graphs.clear();
+  for (hipEvent_t e : {s->ev_done, s->ev_lat[0], s->ev_lat[1], s->ev_lat[2]})
+    if (e) (void)hipEventDestroy(e);
+  for (hipStream_t st : {s->st_main, s->st_lat[0], s->st_lat[1]})
+    if (st) (void)hipStreamDestroy(st);
+  delete s;
+}
+
+int graph_mode();
+
+// Release a slot's latency-schedule streams and events (made again on its next batch of one).
+void slot_drop_lowlat(ProofSlot* s) {
+  for (hipStream_t& st : s->st_lat)
+    if (st) {
+      (void)hipStreamSynchronize(st);
+      (void)hipStreamDestroy(st);
+      st = nullptr;
+    }
+  for (hipEvent_t& e : s->ev_lat)
+    if (e) {
+      (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+}
+
+hipError_t slot_create(zkfl_key* k, ProofSlot** out) {
+  ProofSlot* s = new ProofSlot();
+  *out = s;
+  const size_t nV = k->nVars, n = k->n;
+  const size_t cap1 = std::max<size_t>({k->bA.n, k->bB1.n, k->bCH.n});
+  hipStream_t st = k->ctx->st;
+  // One stream per slot: a slot's proof is a serial chain and throughput comes from many slots
+  // (measured on MI355X, 24 HW queues: 16 slots x 1 stream 238-241 proofs/s vs 8 slots x 3 streams
+  // 216-217).
+  ZK_CHECK(hipStreamCreateWithFlags(&s->st_main, hipStreamNonBlocking));
+  ZK_CHECK(hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming));
+  const int c = k->msm_c;
+  ZK_CHECK(msm_scratch_alloc(s->g1s, cap1, c, st));
+#if ZK_KNOCKOUT & 2
+  for (MsmScratch<FqOps>& x : s->g1s_ko) {  // zeroed: an index past a stale sort is base 0
+    ZK_CHECK(msm_scratch_alloc(x, cap1, c, st));
+    ZK_CHECK(hipMemsetAsync(x.keys_out, 0, cap1 * msm_w_of(c) * sizeof(uint16_t), st));
+    ZK_CHECK(hipMemsetAsync(x.vals_out, 0, cap1 * msm_w_of(c) * sizeof(uint32_t), st));
+  }
+#endif
+  // tail 2 is C + H's; tail 3 only serves the parity hook, which runs the C + H MSM twice (C, then H)
+  const size_t caps[4] = {k->bA.n, k->bB1.n, k->bCH.n, k->bCH.n};
+  for (int i = 0; i < 4; i++) ZK_CHECK(msm_tail_alloc(s->g1t[i], caps[i], c));
+  ZK_CHECK(msm_scratch_alloc(s->g2s, k->bB2.n, c, st));
+  ZK_CHECK(msm_tail_alloc(s->g2t, k->bB2.n, c));
+  if (k->share_b && !ZK_KNOCKOUT) {
+    ZK_CHECK(hipFree(s->g2t.nnz));
+    s->g2t.nnz = s->g1t[1].nnz;
+    s->nnz_alias = true;
+  }
+  if (graph_mode()) ZK_CHECK(hipMalloc(&s->w_stage, nV * 32));
+  if (k->front) {  // A's and B's own sort scratch (C + H sorts in g1s)
+    ZK_CHECK(msm_scratch_alloc(s->g1s_a, k->bA.n, c, st));
+    ZK_CHECK(msm_scratch_alloc(s->g1s_b, k->bB1.n, c, st));
+  }
+  ZK_CHECK(hipMalloc(&s->h, (n + 4) * 32));   // h, then the extra slots (the merged C+H MSM's scalars)
+  s->extra = s->h + n;
+  ZK_CHECK(hipMalloc(&s->abc, n * 3 * 32));
+  const size_t abc_chunks = (k->K + ABC_L - 1) / ABC_L + 1;
+  ZK_CHECK(hipMalloc(&s->abc_head, abc_chunks * 32));
+  ZK_CHECK(hipMalloc(&s->abc_tail, abc_chunks * 32));
+  ZK_CHECK(hipMalloc(&s->res, 5 * sizeof(G1P)));
+  ZK_CHECK(hipMalloc(&s->resB2, sizeof(G2P)));
+  ZK_CHECK(hipMalloc(&s->d_rs, 2 * 32 + 4 * sizeof(GlvScalar)));
+  ZK_CHECK(hipMalloc(&s->d_parts, PART_WORDS * 4));
+  // coherent (fine-grained): the proof chain reads r, s and the GLV halves from it and writes the
+  // proof into it directly (k_proof_start, k_assemble*), so no copy launches open or close a proof
+  ZK_CHECK(hipHostMalloc(&s->pinned, 2048, hipHostMallocCoherent));
+  return hipStreamSynchronize(st);
+}
+
+}  // namespace
+
+int zkfl::get_slot(zkfl_key* k, size_t idx, ProofSlot** out) {
+  size_t want = idx % (size_t)k->max_slots;
+  while (k->slots.size() <= want) {
+    ProofSlot* s = nullptr;
+    hipError_t e = slot_create(k, &s);
+    if (e != hipSuccess) {
+      slot_release(s);
+      return hip_fail(e, "proof slot allocation");
+    }
+    s->index = (int)k->slots.size();
+    k->slots.push_back(s);
+  }
+  *out = k->slots[want];
+  return ZKFL_OK;
+}
+
+// Witnesses of the single-key full-prove entry points, computed G (= the key's slots) jobs at a
+// time by ONE batched launch sequence of the witness engine on the key's witness stream, ahead of
+// the slots that prove them: group g is computed into buffer set g % 3 while the slots prove
+// group g - 1 (when group g + 1 is enqueued, the slots have drained group g - 2, so its set is
+// free).  Per-slot witnesses cost ~25 small launches per proof on the slot's stream, each a
+// permutation-latency chain; batched, a group's 15 levels cost as much as one witness's.
+// Witness sets of a key's pipe: group g uses set g % WIT_SETS; groups run up to WIT_SETS - 2 ahead
+// of the group the key's slots start (full_prove_piped)
+constexpr int WIT_SETS = 4;
+struct WitPipe {
+  struct Set {
+    Fr* W = nullptr;          // [G][nw] Montgomery scratch
+    Fr* d = nullptr;          // [G][nw] std-form witnesses = the proofs' scalars
+    uint32_t* in = nullptr;   // [G][n_in x 8]
+    uint32_t* fail = nullptr; // [G]
+    Fr** outs = nullptr;      // [G] device pointers into d
+    uint8_t* pin_in = nullptr;
+    hipEvent_t ev = nullptr;  // the group's witnesses are complete
+  };
+  size_t G = 0, nw = 0, n_in = 0;
+  hipStream_t st = nullptr;
+  Set set[WIT_SETS];
+};
+
+namespace {
+
+void wpipe_release(WitPipe* p) {
+  if (!p) return;
+  if (p->st) (void)hipStreamSynchronize(p->st);
+  for (auto& b : p->set) {
+    for (void* q : {(void*)b.W, (void*)b.d, (void*)b.in, (void*)b.fail, (void*)b.outs})
+      if (q) (void)hipFree(q);
+    if (b.pin_in) (void)hipHostFree(b.pin_in);
+    if (b.ev) (void)hipEventDestroy(b.ev);
+  }
+  if (p->st) (void)hipStreamDestroy(p->st);
+  delete p;
+}
+
+}  // namespace
+
+void zkfl::key_release_slots(zkfl_key* k) {
+  wpipe_release(k->wpipe);
+  k->wpipe = nullptr;
+  for (ProofSlot* s : k->slots) slot_release(s);
+  k->slots.clear();
+}
+
+namespace {
+
+// The key's pipe for groups of G witnesses of nw wires and n_in inputs (kept between calls).
+hipError_t wpipe_get(zkfl_key* k, size_t G, size_t nw, size_t n_in, WitPipe** out) {
+  WitPipe* p = k->wpipe;
+  if (p && p->G == G && p->nw == nw && p->n_in == n_in) {
+    *out = p;
+    return hipSuccess;
+  }
+  wpipe_release(p);
+  k->wpipe = p = new WitPipe();
+  p->G = G;
+  p->nw = nw;
+  p->n_in = n_in;
+  ZK_CHECK(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
+  for (auto& b : p->set) {
+    ZK_CHECK(hipMalloc(&b.W, G * nw * 32));
+    ZK_CHECK(hipMalloc(&b.d, G * nw * 32));
+    ZK_CHECK(hipMalloc(&b.in, G * n_in * 32 + 16));
+    ZK_CHECK(hipMalloc(&b.fail, G * 4));
+    ZK_CHECK(hipMalloc(&b.outs, G * sizeof(Fr*)));
+    ZK_CHECK(hipHostMalloc(&b.pin_in, G * n_in * 32 + 16));
+    ZK_CHECK(hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
+    std::vector<Fr*> ptrs(G);
+    for (size_t j = 0; j < G; j++) ptrs[j] = b.d + j * nw;
+    ZK_CHECK(hipMemcpy(b.outs, ptrs.data(), G * sizeof(Fr*), hipMemcpyHostToDevice));
+  }
+  *out = p;
+  return hipSuccess;
+}
+
+int get_rs(const uint8_t* rs, uint32_t out[16]) {
+  if (rs) {
+    memcpy(out, rs, 64);
+    if (!fr_lt_r(out) || !fr_lt_r(out + 8)) return fail(ZKFL_E_ARG, "r/s must be < r");
+    return ZKFL_OK;
+  }
+  // CSPRNG, rejection-sample below r (snarkjs: Fr.random())
+  for (int k = 0; k < 2; k++) {
+    for (int tries = 0;; tries++) {
+      uint8_t b[32];
+      if (getrandom(b, 32, 0) != 32) return fail(ZKFL_E_DEVICE, "getrandom failed");
+      b[31] &= 0x3f;  // < 2^254
+      memcpy(out + 8 * k, b, 32);
+      if (fr_lt_r(out + 8 * k)) break;
+      if (tries > 64) return fail(ZKFL_E_DEVICE, "rng");
+    }
+  }
+  return ZKFL_OK;
+}
+
+// Enqueue one proof on a slot (asynchronous), a serial chain on the slot's one stream:
+//   r, s + GLV halves, scalar vectors, accumulate A, B1, B2 (B1's sort) and its tail, ABC, coset
+//   NTT x3, join, accumulate C + H, the G1 tails as one batch, assembly (pi_a, pi_b, pi_c) [ev_done]
+// plain = 1 (parity hook): alpha/beta/delta/r/s terms zeroed, nothing assembled.
+// plain = 2 (split proof): the full augmentation (on shard 0's bases), no assembly; the part
+// A' | B1' | B2' | C' + H | infinity goes to pinned + 512 (zkfl_groth16_prove_part_batch).
+// ABC (a, b, c on the domain), the coset NTT of all three and h = a b - c (std form: the H MSM's
+// scalars) for one proof on stream st.
+int enqueue_abc_ntt(zkfl_key* k, ProofSlot* s, const Fr* d_w, hipStream_t st, Profiler* prof) {
+  const size_t n = k->n;
+  int pi = prof->begin("abc", st);
+  if (k->K) {
+    const uint32_t K = (uint32_t)k->K;
+    const AbcTerms T = {k->cols, k->coefs, k->cshift};
+    abc_chunks(st, k->rows, (uint32_t)(2 * n), T, d_w, K, s->abc_head, s->abc_tail, s->abc);
+  }
+  abc_rows(st, k->rows, n, (uint32_t)k->K, s->abc_head, s->abc_tail, s->abc);
+  prof->end(pi, st, (double)k->K);
+  pi = prof->begin("ntt", st);
+  if (!(ZK_KNOCKOUT & 4)) HIP_TRY(ntt_coset_shift(k->ntt, s->abc, 3, n, st), "ntt");
+  prof->end(pi, st, 3.0 * (double)n);
+  join_h(st, s->abc, n, s->h);
+  return ZKFL_OK;
+}
+
+// The latency schedules reduce their buckets with the shorter-chain reduction (msm.h
+// MSM_WSUM_Q_FAST); ZKFL_FAST_WSUM=0 keeps the throughput form (A/B).
+bool lowlat_fast_wsum() {
+  static const bool on = !getenv("ZKFL_FAST_WSUM") || atoi(getenv("ZKFL_FAST_WSUM")) != 0;
+  return on;
+}
+
+// Small keys (domain <= 2^ZKFL_FAST_WSUM_LOGN, default 2^16: config 5's circuits) take the
+// shorter-chain reduction in batches too: their proofs are chains of small latency-bound kernels
+// that leave most of the GPU idle (config-5 wave trace: SIMD share 0.135 with a wave resident 99%
+// of the time), so the reduction's extra waves are free and its shorter chain is not.
+bool small_key_fast_wsum(const zkfl_key* k) {
+  static const int logn = getenv("ZKFL_FAST_WSUM_LOGN") ? atoi(getenv("ZKFL_FAST_WSUM_LOGN")) : 16;
+  return lowlat_fast_wsum() && k->logn <= logn;
+}
+
+// One proof alone (a batch of one: the CLI's `groth16 prove`, the API's prove): its latency is
+// the metric, and the GPU is mostly idle along the one-stream chain, so the two long chains start
+// at once on streams of their own:
+//   main : r, s, tails reset [ev ready] ABC, coset NTT, join, C + H (sort + accumulate), its tail,
+//          wait(B2, T), k_assemble_c, proof D2H [ev_done]
+//   lat0 : wait(ev ready) B sort (own scratch) [ev B sorted] B2 + its tail [ev B2]
+//   lat1 : wait(ev B sorted) B1, A (sort into its own scratch + accumulate), the tails of A and
+//          B1, k_assemble_t (T = s pi_A + r B1, pi_a) [ev T]
+// Same proof bytes as the one-stream schedule (k_assemble_t / _c form the same points).  The
+// round-4 schedule ran A and B1 on the main stream ahead of ABC / NTT (4.10 vs 4.16 ms then); with
+// the row assembly and the divsteps inversions the overlap wins: 3.586 vs 3.712 ms, 3 same-box
+// alternations (profiles/r06_ab_lowlat2.log), and the round-4 one was deleted, with its
+// per-segment graph replay (ZKFL_GRAPH=2: no gain, profiles/r04_ab_lowlat_seg_graphs.log).
+
+// ZKFL_GRAPH (default 1): graph replay of the one-stream proof chain (0: launch kernel by kernel)
+int graph_mode() {
+  static const int m = getenv("ZKFL_GRAPH") ? atoi(getenv("ZKFL_GRAPH")) : 1;
+  return m;
+}
+
+// (the schedule above)
+int enqueue_proof_lowlat(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w) {
+  Profiler* prof = &ctx->prof;
+  hipStream_t st = s->st_main;
+  for (int i = 0; i < 2; i++)
+    if (!s->st_lat[i]) HIP_TRY(hipStreamCreateWithFlags(&s->st_lat[i], hipStreamNonBlocking), "stream");
+  for (int i = 0; i < 3; i++)
+    if (!s->ev_lat[i]) HIP_TRY(hipEventCreateWithFlags(&s->ev_lat[i], hipEventDisableTiming), "event");
+  if (!s->g1s_b.keys_out) HIP_TRY(msm_scratch_alloc(s->g1s_b, k->bB1.n, k->msm_c, st), "B sort scratch");
+  if (!s->g1s_a.keys_out) HIP_TRY(msm_scratch_alloc(s->g1s_a, k->bA.n, k->msm_c, st), "A sort scratch");
+  hipStream_t sb = s->st_lat[0], sa = s->st_lat[1];
+  // ev_lat[0] marks "ready" then (re-recorded on lat0) "B sorted": each wait is enqueued before
+  // the next record, so every wait sees the record it was meant for
+  hipEvent_t ev = s->ev_lat[0], ev_b2 = s->ev_lat[1], ev_t = s->ev_lat[2];
+  const uint32_t* W = (const uint32_t*)d_w;
+  const uint32_t* E = (const uint32_t*)s->extra;
+  MsmTail<FqOps>* tails[3] = {&s->g1t[0], &s->g1t[1], &s->g1t[2]};
+  MsmTail<Fq2Ops>* t2 = &s->g2t;
+  G2P* o2 = s->resB2;
+  HIP_TRY(hipEventRecord(ev, st), "event");  // (tails emptied by k_proof_start)
+  // lat0: B's sort, then B2 and its tail
+  HIP_TRY(hipStreamWaitEvent(sb, ev, 0), "wait");
+  HIP_TRY(msm_sort(k->bB1, s->g1s_b, s->g1t[1].nnz, W, E, sb), "msm B sort");
+  if (!s->nnz_alias)
+    HIP_TRY(hipMemcpyAsync(s->g2t.nnz, s->g1t[1].nnz, sizeof(uint32_t), hipMemcpyDeviceToDevice, sb), "nnz");
+  HIP_TRY(hipEventRecord(ev, sb), "event");
+  HIP_TRY(hipStreamWaitEvent(sa, ev, 0), "wait");
+  HIP_TRY(msm_accumulate_sorted(k->bB2, s->g1s_b.keys_out, s->g1s_b.vals_out, s->g2t, sb, prof,
+                                   "msm_accumulate_g2"), "msm B2");
+  HIP_TRY(msm_tails(&t2, &o2, 1, sb, lowlat_fast_wsum()), "msm B2 tail");
+  HIP_TRY(hipEventRecord(ev_b2, sb), "event");
+  // lat1: B1 (B's pairs), A, their tails, then T = s pi_A + r B1 and pi_a
+  HIP_TRY(msm_accumulate_sorted(k->bB1, s->g1s_b.keys_out, s->g1s_b.vals_out, s->g1t[1], sa, prof,
+                                   "msm_accumulate_g1"), "msm B1");
+  HIP_TRY(msm_accumulate(k->bA, s->g1s_a, s->g1t[0], W, E, sa, prof, "msm_accumulate_g1"), "msm A");
+  {
+    G1P* outs[2] = {s->res + 0, s->res + 1};
+    HIP_TRY(msm_tails(tails, outs, 2, sa, lowlat_fast_wsum()), "msm tails A, B1");
+  }
+  assemble_t(sa, s->res, reinterpret_cast<const GlvScalar*>(reinterpret_cast<const uint8_t*>(s->d_rs) + 64),
+             proof_out(s));
+  HIP_TRY(hipEventRecord(ev_t, sa), "event");
+  // main: ABC / NTT / h, C + H and its tail, then pi_c and pi_b
+  {
+    const int rc = enqueue_abc_ntt(k, s, d_w, st, prof);
+    if (rc) return rc;
+  }
+  HIP_TRY(msm_accumulate(k->bCH, s->g1s, s->g1t[2], W, (const uint32_t*)s->h, st, prof, "msm_accumulate_g1"),
+          "msm C+H");
+  {
+    G1P* out2 = s->res + 2;
+    HIP_TRY(msm_tails(&tails[2], &out2, 1, st, lowlat_fast_wsum()), "msm tail C+H");
+  }
+  HIP_TRY(hipStreamWaitEvent(st, ev_b2, 0), "wait");
+  HIP_TRY(hipStreamWaitEvent(st, ev_t, 0), "wait");
+  const int pa = prof->begin("assemble", st);
+  assemble_c(st, s->res, s->resB2, proof_out(s));
+  prof->end(pa, st, 1.0);
+  return ZKFL_OK;
+}
+
+// The device work of one proof on the slot's stream (the latency schedule adds two of its own),
+// after the host has put r, s and the GLV halves into the pinned buffer.
+int enqueue_proof_body(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, int plain, int lowlat) {
+  Profiler* prof = &ctx->prof;
+  hipStream_t st = s->st_main;
+  int pp = prof->begin("prove", st);
+  const bool lowlat_path = lowlat && plain == 0 && k->share_b && !prof->serialize && !ZK_KNOCKOUT;
+  // C + H as one MSM into tail 2 (res[2] = C' + H, res[3] = infinity); the parity hook (plain = 1)
+  // returns them apart: C = the C + H MSM over (witness, zero h), H = over (zero witness, h)
+  const bool merge = plain != 1;
+  const bool split_ch = !merge;
+  const int ntails = merge ? 3 : 4;
+  // B1's digit sort also serves B2 (same scalars, same index map), so B2 runs right after B1,
+  // before C + H reuses the sort scratch.  A key whose two index maps differ runs B2 as an MSM of its
+  // own (own sort, own tail).
+  const bool share = k->share_b && !(ZK_KNOCKOUT & 32);
+  {
+    // the tails this chain accumulates into: G1 A, B1, C + H, [H]; G2 B2 when it shares B1's sort
+    // (its own msm_run empties its tail itself)
+    ProofStart ps = {};
+    auto add = [&](void* buckets, size_t bytes, uint32_t* nnz, uint32_t* live) {
+      ps.buckets[ps.n] = static_cast<uint4*>(buckets);
+      ps.nvec[ps.n] = (uint32_t)(bytes / sizeof(uint4));
+      ps.nnz[ps.n] = nnz;
+      ps.live[ps.n] = live;
+      ps.n++;
+    };
+    const size_t nb = msm_nb_of(k->msm_c);
+    for (int i = 0; i < ntails; i++) add(s->g1t[i].buckets, nb * sizeof(G1P), s->g1t[i].nnz, s->g1t[i].live);
+    if (share) add(s->g2t.buckets, nb * sizeof(G2P), s->g2t.nnz, s->g2t.live);
+    uint32_t* res3 = merge ? reinterpret_cast<uint32_t*>(s->res + 3) : nullptr;
+    if (s->w_stage && d_w == s->w_stage) {  // graph replay (enqueue_proof): stage the witness here
+      ps.w_src_host = reinterpret_cast<const uint64_t*>(s->pinned + W_PTR_OFF);
+      ps.w_dst = reinterpret_cast<uint4*>(s->w_stage);
+      ps.w_nvec = (uint32_t)((size_t)k->nVars * 32 / sizeof(uint4));
+    }
+    proof_start(st, reinterpret_cast<const uint32_t*>(s->pinned + 256), reinterpret_cast<uint32_t*>(s->d_rs), s->extra,
+                plain == 1, res3, ps);
+  }
+  if (lowlat_path) {
+    const int rc = enqueue_proof_lowlat(ctx, k, s, d_w);
+    if (rc) return rc;
+    prof->end(pp, st, 1.0);
+    return ZKFL_OK;
+  }
+  const uint32_t* W = (const uint32_t*)d_w;
+  const uint32_t* E = (const uint32_t*)s->extra;
+  MsmTail<FqOps>* tails[4] = {&s->g1t[0], &s->g1t[1], &s->g1t[2], &s->g1t[3]};
+  if (split_ch && !k->dbg_zero) return fail(ZKFL_E_ARG, "parity hook: zeros not allocated");
+  const uint32_t* Z = (const uint32_t*)k->dbg_zero;
+  // Stage order.  Every slot runs the same chain, so under load the slots move as a convoy: the
+  // accumulations fill the GPU one at a time, and the slots that leave them together reach ABC +
+  // NTT together -- the wave timeline (tools/wtrace.py) showed stretches of ~4 ms with no
+  // accumulation resident at all.  Staggered (the default; ZKFL_STAGGER=0 turns it off): odd slots
+  // run ABC + NTT before their witness-scalar MSMs instead of after, so their light phase falls
+  // beside the others' heavy one (+2.3 %, 407.5 vs 398.6 proofs/s, 3 same-box alternations).
+  static const int stagger = getenv("ZKFL_STAGGER") ? atoi(getenv("ZKFL_STAGGER")) : 1;
+  const bool light_first = stagger && (s->index & 1) && !prof->serialize;
+  // Small keys: the G2 tail joins the G1 tails' launches (msm_tails_joint) instead of running right
+  // after B2 -- config 5 2,712 vs 2,385 proofs/s (3 same-box alternations); the metric key keeps the
+  // separate tails (M 433 vs 439 and 431 vs 433 with them joint, two boxes:
+  // profiles/r06_ab_joint_tails.log, r06_ab_front.log)
+  const bool joint = share && k->front;
+  if (!share && !(ZK_KNOCKOUT & 32))
+    HIP_TRY(msm_run(k->bB2, s->g2s, s->g2t, W, E, s->resB2, st, prof, "msm_accumulate_g2"), "msm B2");
+  auto abc_ntt = [&]() { return enqueue_abc_ntt(k, s, d_w, st, prof); };
+  // main: the witness-scalar G1 MSMs, then ABC / NTT / H, then all four G1 tails in one batch
+#if ZK_KNOCKOUT & 2
+  MsmScratch<FqOps>&sA = s->g1s_ko[0], &sB = s->g1s_ko[1], &sCH = s->g1s_ko[2];
+#else
+  MsmScratch<FqOps>&sA = s->g1s, &sB = s->g1s, &sCH = s->g1s;
+#endif
+  // small keys: ABC / NTT, then A, B1 and C + H sorted together and accumulated in one launch, B2
+  // from B1's pairs (their proofs are chains of latency-bound launches: fewer links, shorter chain;
+  // config 5 2,802 vs 2,748 proofs/s, 3 same-box alternations, profiles/r06_ab_front.log)
+  const bool front = joint && merge && !(ZK_KNOCKOUT & 2) && s->g1s_a.keys_out && s->g1s_b.keys_out;
+  if (front) {
+    const int rc = abc_ntt();
+    if (rc) return rc;
+    const MsmBases<FqOps>* bs[3] = {&k->bA, &k->bB1, &k->bCH};
+    MsmScratch<FqOps>* ss[3] = {&s->g1s_a, &s->g1s_b, &s->g1s};
+    uint32_t* nn[3] = {s->g1t[0].nnz, s->g1t[1].nnz, s->g1t[2].nnz};
+    const uint32_t* sc[3] = {W, W, W};
+    const uint32_t* ex[3] = {E, E, (const uint32_t*)s->h};
+    HIP_TRY(msm_sort_multi(bs, ss, nn, sc, ex, 3, st), "msm A, B1, C+H sorts");
+    const uint16_t* kk[3] = {ss[0]->keys_out, ss[1]->keys_out, ss[2]->keys_out};
+    const uint32_t* vv[3] = {ss[0]->vals_out, ss[1]->vals_out, ss[2]->vals_out};
+    HIP_TRY(msm_accumulate_sorted_multi(bs, kk, vv, tails, 3, st), "msm A, B1, C+H");
+    if (!s->nnz_alias)
+      HIP_TRY(hipMemcpyAsync(s->g2t.nnz, s->g1t[1].nnz, sizeof(uint32_t), hipMemcpyDeviceToDevice, st), "nnz");
+    HIP_TRY(msm_accumulate_sorted(k->bB2, ss[1]->keys_out, ss[1]->vals_out, s->g2t, st, prof, "msm_accumulate_g2"),
+            "msm B2");
+  }
+  if (light_first && !front) {
+    const int rc = abc_ntt();
+    if (rc) return rc;
+  }
+  if (!front) HIP_TRY(msm_accumulate(k->bA, sA, s->g1t[0], W, E, st, prof, "msm_accumulate_g1"), "msm A");
+  if (front) {
+  } else if (share) {
+    MsmTail<Fq2Ops>* t2 = &s->g2t;
+    G2P* o2 = s->resB2;
+    HIP_TRY(msm_sort(k->bB1, sB, s->g1t[1].nnz, W, E, st), "msm B1 sort");
+    HIP_TRY(msm_accumulate_sorted(k->bB1, sB.keys_out, sB.vals_out, s->g1t[1], st, prof,
+                                     "msm_accumulate_g1"), "msm B1");
+    if (!s->nnz_alias)
+      HIP_TRY(hipMemcpyAsync(s->g2t.nnz, s->g1t[1].nnz, sizeof(uint32_t), hipMemcpyDeviceToDevice, st), "nnz");
+    HIP_TRY(msm_accumulate_sorted(k->bB2, sB.keys_out, sB.vals_out, s->g2t, st, prof,
+                                     "msm_accumulate_g2"), "msm B2");
+    if (!joint) HIP_TRY(msm_tails(&t2, &o2, 1, st, small_key_fast_wsum(k)), "msm B2 tail");
+  } else {
+    HIP_TRY(msm_accumulate(k->bB1, sB, s->g1t[1], W, E, st, prof, "msm_accumulate_g1"), "msm B1");
+  }
+  if (split_ch)
+    HIP_TRY(msm_accumulate(k->bCH, s->g1s, s->g1t[2], W, Z, st, prof, "msm_accumulate_g1"), "msm C");
+  if (!light_first && !front) {
+    const int rc = abc_ntt();
+    if (rc) return rc;
+  }
+  if (front) {
+  } else if (merge) {
+    HIP_TRY(msm_accumulate(k->bCH, sCH, s->g1t[2], W, (const uint32_t*)s->h, st, prof, "msm_accumulate_g1"),
+            "msm C+H");
+  } else {
+    HIP_TRY(msm_accumulate(k->bCH, s->g1s, s->g1t[3], Z, (const uint32_t*)s->h, st, prof, "msm_accumulate_g1"),
+            "msm H");
+  }
+  {
+    G1P* outs[4] = {s->res + 0, s->res + 1, s->res + 2, s->res + 3};
+    if (joint) {
+      MsmTail<Fq2Ops>* t2 = &s->g2t;
+      G2P* o2 = s->resB2;
+      HIP_TRY(msm_tails_joint(tails, outs, ntails, &t2, &o2, 1, st, small_key_fast_wsum(k)), "msm tails (G1 + G2)");
+    } else {
+      HIP_TRY(msm_tails(tails, outs, ntails, st, small_key_fast_wsum(k)), "msm tails");
+    }
+  }
+  if (plain == 2) {
+    part_out(st, s->res, s->resB2, s->d_parts);
+    HIP_TRY(hipMemcpyAsync(s->pinned + 512, s->d_parts, PART_WORDS * 4, hipMemcpyDeviceToHost, st), "download part");
+  }
+  if (!plain && !(ZK_KNOCKOUT & 1)) {
+    const int pa = prof->begin("assemble", st);
+    assemble(st, 1, s->res, s->resB2, reinterpret_cast<const GlvScalar*>(reinterpret_cast<const uint8_t*>(s->d_rs) + 64),
+             proof_out(s));
+    prof->end(pa, st, 1.0);
+  }
+  prof->end(pp, st, 1.0);
+  return ZKFL_OK;
+}
+
+// Graph replay of the one-stream chain (the default; ZKFL_GRAPH=0 launches kernel by kernel;
+// config 5 +3.5%, 1894 vs 1831 proofs/s, M +0.6% inside the spread, 3 same-box alternations,
+// profiles/r04_ab_c5_small_keys.log, r04_ab_m_graph_target.log): a slot captures its proof's ~40 launches
+// once per witness address (enqueue_proof passes the slot's witness stage, so once per slot) and
+// then launches the graph -- one host call per proof instead of one per kernel.  Kernel arguments
+// are the slot's own buffers, the key's and the witness address, all fixed per cache entry; r and s
+// reach the device through the captured copy from the slot's pinned buffer.
+int enqueue_proof_graph(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, int plain) {
+  hipStream_t st = s->st_main;
+  ProofSlot::Graph* gr = nullptr;
+  for (auto& x : s->graphs)
+    if (x.w == d_w) gr = &x;
+  if (!gr) {
+    if (s->graphs.size() >= 8) {  // bounded cache: drop the oldest
+      ProofSlot::Graph& o = s->graphs.front();
+      if (o.ex) (void)hipGraphExecDestroy(o.ex);
+      if (o.g) (void)hipGraphDestroy(o.g);
+      s->graphs.erase(s->graphs.begin());
+    }
+    ProofSlot::Graph ng;
+    ng.w = d_w;
+    HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal), "begin capture");
+    const int rc = enqueue_proof_body(ctx, k, s, d_w, plain, 0);
+    const hipError_t ec = hipStreamEndCapture(st, &ng.g);
+    if (rc) {
+      if (ng.g) (void)hipGraphDestroy(ng.g);
+      return rc;
+    }
+    HIP_TRY(ec, "end capture");
+    const hipError_t ei = hipGraphInstantiate(&ng.ex, ng.g, nullptr, nullptr, 0);
+    if (ei != hipSuccess) {
+      (void)hipGraphDestroy(ng.g);
+      return hip_fail(ei, "graph instantiate");
+    }
+    s->graphs.push_back(ng);
+    gr = &s->graphs.back();
+  }
+  HIP_TRY(hipGraphLaunch(gr->ex, st), "graph launch");
+  return ZKFL_OK;
+}
+
+int enqueue_proof(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, const uint32_t rs_host[16], int plain,
+                  int lowlat = 0) {
+  Profiler* prof = &ctx->prof;
+  memcpy(s->pinned + 256, rs_host, 64);
+  GlvScalar* ks = reinterpret_cast<GlvScalar*>(s->pinned + 320);
+  glv_split(rs_host + 8, ks[0], ks[1]);  // s -> s1, s2 (for pi_A, phi(pi_A))
+  glv_split(rs_host, ks[2], ks[3]);      // r -> r1, r2 (for B1, phi(B1))
+  // graph replay from a slot's second proof on (a one-off proof pays no capture); the witness is
+  // staged into the slot's own buffer so the captured kernel arguments hold for every witness
+  const bool graph = graph_mode() && s->w_stage && !lowlat && plain == 0 && !prof->on && !prof->serialize &&
+                     k->share_b && !ZK_KNOCKOUT && s->direct_proofs > 0;
+  int rc;
+  if (graph) {
+    // k_proof_start copies the witness into the stage from the address left here
+    const uint64_t src = reinterpret_cast<uint64_t>(d_w);
+    memcpy(s->pinned + W_PTR_OFF, &src, sizeof(src));
+    rc = enqueue_proof_graph(ctx, k, s, s->w_stage, plain);
+  } else {
+    s->direct_proofs++;
+    rc = enqueue_proof_body(ctx, k, s, d_w, plain, lowlat);
+  }
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(s->ev_done, s->st_main), "event");
+  HIP_TRY(hipGetLastError(), "launch");
+  return ZKFL_OK;
+}
+
+// Host wait for a device event.  hipEventSynchronize on these (non-blocking-sync) events spins a
+// host core for the whole wait: it was most of config 5's host CPU per proof (0.55-0.57 ms, 1.2
+// cores busy at ~2,100 proofs/s).  A batch (poll = true) polls instead, sleeping ZKFL_WAIT_US
+// (default 50) microseconds between queries: 0.13-0.16 ms per proof, 0.3 cores, throughput within
+// the spread (2,091 vs 2,095 proofs/s, 3 same-box alternations, profiles/r05_ab_c5_fold_wait.log,
+// which A/Bs the waits beside a since-removed fold knob);
+// the scheduler refills a freed slot up to that much later, ~0.1% of an M step.  A proof alone (the
+// latency path) keeps the spin.  ZKFL_WAIT_US=0 spins everywhere.
+static hipError_t host_wait(hipEvent_t ev, bool poll) {
+  static const int us = getenv("ZKFL_WAIT_US") ? atoi(getenv("ZKFL_WAIT_US")) : 50;
+  if (us <= 0 || !poll) return hipEventSynchronize(ev);
+  for (;;) {
+    const hipError_t e = hipEventQuery(ev);
+    if (e != hipErrorNotReady) return e;
+    std::this_thread::sleep_for(std::chrono::microseconds(us));
+  }
+}
+
+int wait_slot(ProofSlot* s, bool poll = false) {
+  HIP_TRY(host_wait(s->ev_done, poll), "sync");
+  if (s->out_proof) memcpy(s->out_proof, s->pinned, 256);
+  if (s->out_part) memcpy(s->out_part, s->pinned + 512, PART_WORDS * 4);
+  s->busy = false;
+  return ZKFL_OK;
+}
+
+// One proof of a batch: a device-resident witness, complete once w_ready is (nullptr: already).
+// Jobs of one batch may use different keys.
+struct Job {
+  zkfl_key* key = nullptr;
+  const Fr* w = nullptr;
+  hipEvent_t w_ready = nullptr;  // the witness group of the full-prove pipe (full_prove_piped)
+  const uint8_t* rs = nullptr;  // 64 B or nullptr (CSPRNG)
+  uint8_t* proof_out = nullptr;
+  uint8_t* part_out = nullptr;  // split proof: this shard's part instead of a proof
+};
+
+// The batch scheduler behind every prove entry point: job i goes to the next slot of its key
+// (round robin per key), a busy slot is drained first, so up to max_slots proofs per key are in
+// flight and proofs of different keys (e.g. the training and secure-aggregation circuits of one
+// federated round) overlap on the device.  job(i, Job&) fills the i-th job.
+template <class GetJob>
+int run_jobs(zkfl_ctx* ctx, size_t n, GetJob job) {
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  struct PerKey {
+    zkfl_key* key;
+    size_t issued = 0;  // proofs issued in this batch
+  };
+  std::vector<PerKey> cursor;
+  // a batch of one proof runs the low-latency schedule (ZKFL_LOWLAT=0: the one-stream chain)
+  static const int lowlat = getenv("ZKFL_LOWLAT") ? atoi(getenv("ZKFL_LOWLAT")) : 1;
+  auto issue = [&](PerKey& pk, size_t i, const Job& J, const uint32_t* rsl) -> int {
+    ProofSlot* s = nullptr;
+    int rc = get_slot(J.key, pk.issued++, &s);
+    if (rc) return rc;
+    if (s->busy) {
+      rc = wait_slot(s, n > 1);
+      if (rc) return rc;
+    }
+    s->job = i;
+    s->out_proof = J.part_out ? nullptr : J.proof_out;
+    s->out_part = J.part_out;
+    if (J.w_ready) {
+      hipError_t e = hipStreamWaitEvent(s->st_main, J.w_ready, 0);
+      if (e != hipSuccess) return hip_fail(e, "wait for the witness group");
+    }
+    rc = enqueue_proof(ctx, J.key, s, J.w, rsl, J.part_out ? 2 : 0, n == 1 ? lowlat : 0);
+    if (rc) return rc;
+    s->busy = true;
+    return ZKFL_OK;
+  };
+  int rc = ZKFL_OK;
+  for (size_t i = 0; i < n && rc == ZKFL_OK; i++) {
+    Job J;
+    rc = job(i, J);
+    if (rc) break;
+    if (J.key->nshards != 1 && !J.part_out) {  // its MSMs are one shard's share: no whole proof
+      rc = fail(ZKFL_E_ARG, "this key is shard " + std::to_string(J.key->shard) + " of " +
+                                std::to_string(J.key->nshards) +
+                                " of a split proof: prove parts (zkfl_groth16_prove_part_batch) and assemble them");
+      break;
+    }
+    uint32_t rsl[16];
+    rc = get_rs(J.rs, rsl);
+    if (rc) break;
+    size_t c = 0;
+    while (c < cursor.size() && cursor[c].key != J.key) c++;
+    if (c == cursor.size()) {
+      cursor.emplace_back();
+      cursor.back().key = J.key;
+    }
+    rc = issue(cursor[c], i, J, rsl);
+  }
+  for (auto& pk : cursor) {
+    for (ProofSlot* s : pk.key->slots)
+      if (s->busy) {
+        int r2 = wait_slot(s, n > 1);
+        if (rc == ZKFL_OK) rc = r2;
+      }
+  }
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zkfl_groth16_prove_resident(zkfl_ctx* ctx, zkfl_key* key, const zkfl_witness* w, const uint8_t* rs,
+                                uint8_t proof_out[256]) {
+  return zkfl_groth16_prove_batch(ctx, key, 1, &w, rs, proof_out);
+}
+
+int zkfl_key_set_slots(zkfl_key* key, int slots) {
+  if (!key || slots < 1 || slots > 32) return fail(ZKFL_E_ARG, "slots must be in 1..32");
+  (void)hipSetDevice(key->ctx->device);
+  for (ProofSlot* s : key->slots) {
+    if (s->busy) return fail(ZKFL_E_ARG, "slots busy");
+  }
+  while ((int)key->slots.size() > slots) {
+    slot_release(key->slots.back());
+    key->slots.pop_back();
+  }
+  // a slot's latency-schedule streams (made by a batch of one) hold HW queues: with many slots
+  // they would push the slots' own streams past the ~24 HW queues and make slots share them
+  // (a latency pass on a one-slot key before a 20-slot run: 395 vs 415 proofs/s)
+  if (slots > 1)
+    for (ProofSlot* s : key->slots) slot_drop_lowlat(s);
+  key->max_slots = slots;
+  return ZKFL_OK;
+}
+
+int zkfl_groth16_prove_batch(zkfl_ctx* ctx, zkfl_key* key, size_t n, const zkfl_witness* const* w,
+                             const uint8_t* rs, uint8_t* proofs_out) {
+  if (!ctx || !key || (!w && n) || (!proofs_out && n)) return fail(ZKFL_E_ARG, "null argument");
+  for (size_t i = 0; i < n; i++) {
+    if (!w[i] || w[i]->key != key) return fail(ZKFL_E_MISMATCH, "witness uploaded for another key");
+  }
+  return run_jobs(ctx, n, [&](size_t i, Job& J) {
+    J.key = key;
+    J.w = w[i]->d;
+    J.rs = rs ? rs + 64 * i : nullptr;
+    J.proof_out = proofs_out + 256 * i;
+    return ZKFL_OK;
+  });
+}
+
+int zkfl_groth16_prove_part_batch(zkfl_ctx* ctx, zkfl_key* key, size_t n, const zkfl_witness* const* w,
+                                  const uint8_t* rs, uint8_t* parts_out) {
+  if (!ctx || !key || (n && (!w || !rs || !parts_out))) return fail(ZKFL_E_ARG, "prove_part: null argument");
+  for (size_t i = 0; i < n; i++) {
+    if (!w[i] || w[i]->key != key) return fail(ZKFL_E_MISMATCH, "witness uploaded for another key");
+  }
+  return run_jobs(ctx, n, [&](size_t i, Job& J) {
+    J.key = key;
+    J.w = w[i]->d;
+    J.rs = rs + 64 * i;
+    J.part_out = parts_out + PART_WORDS * 4 * i;
+    return ZKFL_OK;
+  });
+}
+
+int zkfl_groth16_assemble(zkfl_ctx* ctx, size_t n, size_t n_parts, const uint8_t* parts, const uint8_t* rs,
+                          uint8_t* proofs_out) {
+  if (!ctx || (n && (!parts || !rs || !proofs_out)) || n_parts < 1 || n_parts > 1024)
+    return fail(ZKFL_E_ARG, "assemble: bad arguments");
+  if (n == 0) return ZKFL_OK;
+  // every coordinate canonical (< q): the parts cross a process boundary
+  for (size_t i = 0; i < n * n_parts * (PART_WORDS / 8); i++)
+    if (!fq_lt_q(reinterpret_cast<const uint32_t*>(parts + 32 * i)))
+      return fail(ZKFL_E_ARG, "assemble: part coordinate " + std::to_string(i) + " is not < q");
+  std::vector<uint8_t> ks(n * 4 * sizeof(GlvScalar));
+  for (size_t i = 0; i < n; i++) {
+    uint32_t rsl[16];
+    int rc = get_rs(rs + 64 * i, rsl);
+    if (rc) return rc;
+    GlvScalar* k = reinterpret_cast<GlvScalar*>(ks.data()) + 4 * i;
+    glv_split(rsl + 8, k[0], k[1]);  // s -> pi_A's multiplier
+    glv_split(rsl, k[2], k[3]);      // r -> B1's multiplier
+  }
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = ctx->st;
+  // one device buffer, carved: parts | res (5 G1P per proof) | resB2 | GLV halves | proofs | bad flag
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_res = up(n * n_parts * PART_WORDS * 4), o_b2 = o_res + up(n * 5 * sizeof(G1P)),
+               o_ks = o_b2 + up(n * sizeof(G2P)), o_pf = o_ks + up(ks.size()), o_bad = o_pf + up(n * 256),
+               total = o_bad + 4;
+  if (total > ctx->asm_cap) {
+    if (ctx->asm_buf) (void)hipFree(ctx->asm_buf);
+    ctx->asm_buf = nullptr;
+    ctx->asm_cap = 0;
+    HIP_TRY(hipMalloc(&ctx->asm_buf, total), "assemble buffers");
+    ctx->asm_cap = total;
+  }
+  uint8_t* base = static_cast<uint8_t*>(ctx->asm_buf);
+  void *d_parts = base, *d_res = base + o_res, *d_b2 = base + o_b2, *d_ks = base + o_ks, *d_proof = base + o_pf;
+  uint32_t* d_bad = reinterpret_cast<uint32_t*>(base + o_bad);
+  uint32_t bad = 0;
+  hipError_t e = hipMemcpyAsync(d_parts, parts, n * n_parts * PART_WORDS * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_ks, ks.data(), ks.size(), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 4, st);
+  if (e == hipSuccess) {
+    parts_sum(st, (uint32_t)n, (const uint32_t*)d_parts, (int)n_parts, (G1P*)d_res, (G2P*)d_b2, d_bad);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hip_fail(e, "assemble");
+  if (bad) return fail(ZKFL_E_ARG, "assemble: a part holds a point that is not on its curve");
+  assemble(st, (uint32_t)n, (const G1P*)d_res, (const G2P*)d_b2, (const GlvScalar*)d_ks, (uint32_t*)d_proof);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(proofs_out, d_proof, n * 256, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hip_fail(e, "assemble");
+  return ZKFL_OK;
+}
+
+int zkfl_groth16_prove_multi(zkfl_ctx* ctx, size_t n, zkfl_key* const* keys, const zkfl_witness* const* w,
+                             const uint8_t* rs, uint8_t* proofs_out) {
+  if (!ctx || (n && (!keys || !w || !proofs_out))) return fail(ZKFL_E_ARG, "prove_multi: null argument");
+  for (size_t i = 0; i < n; i++) {
+    if (!keys[i] || keys[i]->ctx != ctx) return fail(ZKFL_E_ARG, "prove_multi: key of another context");
+    if (!w[i] || w[i]->key != keys[i]) return fail(ZKFL_E_MISMATCH, "prove_multi: witness uploaded for another key");
+  }
+  return run_jobs(ctx, n, [&](size_t i, Job& J) {
+    J.key = keys[i];
+    J.w = w[i]->d;
+    J.rs = rs ? rs + 64 * i : nullptr;
+    J.proof_out = proofs_out + 256 * i;
+    return ZKFL_OK;
+  });
+}
+
+static int full_prove_check(const zkfl_ctx* ctx, const zkfl_key* key, const zkfl_wprog* prog, size_t n,
+                            const uint8_t* inputs, size_t* n_in) {
+  if (!key || !prog || (n && !inputs)) return fail(ZKFL_E_ARG, "full_prove: null argument");
+  if (key->ctx != ctx || prog->ctx != ctx) return fail(ZKFL_E_ARG, "full_prove: key/program of another context");
+  uint32_t nw = 0, n_in32 = 0, npub = 0;
+  wprog_info(prog->p, &nw, &n_in32, &npub);
+  if (nw != key->nVars || npub != key->nPub)
+    return fail(ZKFL_E_MISMATCH, "witness program does not match the proving key (nVars / nPublic)");
+  *n_in = n_in32;
+  std::string err;
+  if (!wprog_inputs_ok(prog->p, n, inputs, err)) return fail(ZKFL_E_ARG, err);
+  return ZKFL_OK;
+}
+
+// Full prove through the keys' witness pipes: for each key, groups of G = its slots witnesses one
+// group ahead of its slots (WitPipe); a proof waits on its group's event.  Job i uses key_of(i),
+// program prog_of(i) (nVars / inputs of that key), get_input(i, &ptr) yields its input vector
+// (n_in x 32 B std form, < r; called in increasing i per key), pub_of(i) its public-signal
+// destination (nullable).
+extern "C++" {
+template <class KeyOf, class ProgOf, class GetInput, class PubOf>
+int full_prove_piped(zkfl_ctx* ctx, size_t n, KeyOf key_of, ProgOf prog_of, GetInput get_input, const uint8_t* rs,
+                     uint8_t* proofs_out, PubOf pub_of) {
+  if (n == 0) return ZKFL_OK;
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  struct PerKey {
+    zkfl_key* key;
+    const WProg* prog;
+    size_t G = 0, n_in = 0, groups = 0;
+    WitPipe* pipe = nullptr;
+    std::vector<size_t> jobs;  // global indices, in order
+  };
+  std::vector<PerKey> ks;
+  std::vector<size_t> kidx(n), local(n), off(n + 1, 0);
+  for (size_t i = 0; i < n; i++) {
+    zkfl_key* k = key_of(i);
+    size_t c = 0;
+    while (c < ks.size() && ks[c].key != k) c++;
+    if (c == ks.size()) {
+      PerKey pk;
+      pk.key = k;
+      pk.prog = prog_of(i);
+      uint32_t nw = 0, nin = 0, np = 0;
+      wprog_info(pk.prog, &nw, &nin, &np);
+      pk.n_in = nin;
+      // one group >= the proofs a key holds in flight: the witness sets'
+      // reuse (enqueue_group) relies on it.  ZKFL_WIT_GROUP=m: m times that (a witness launch
+      // serves m x as many witnesses; its kernels are latency-bound, so they take about as long)
+      static const int wg = getenv("ZKFL_WIT_GROUP") ? std::max(1, atoi(getenv("ZKFL_WIT_GROUP"))) : 1;
+      pk.G = (size_t)k->max_slots * wg;
+      ks.push_back(pk);
+    }
+    kidx[i] = c;
+    local[i] = ks[c].jobs.size();
+    ks[c].jobs.push_back(i);
+    off[i + 1] = off[i] + 4 + (size_t)k->nPub * 32;  // pinned record: fail flag | public signals
+  }
+  for (auto& pk : ks) {
+    pk.groups = (pk.jobs.size() + pk.G - 1) / pk.G;
+    HIP_TRY(wpipe_get(pk.key, pk.G, pk.key->nVars, pk.n_in, &pk.pipe), "witness pipe allocation");
+  }
+  uint8_t* pin_out = nullptr;
+  HIP_TRY(hipHostMalloc(&pin_out, off[n] + 16), "pinned witness outputs");
+  // groups enqueued ahead of the one the slots start (ZKFL_WIT_AHEAD, 1..WIT_SETS - 2): a group
+  // is computed while the slots run the `ahead` groups before it
+  static const size_t ahead = (size_t)std::clamp(getenv("ZKFL_WIT_AHEAD") ? atoi(getenv("ZKFL_WIT_AHEAD")) : 2, 1,
+                                                 WIT_SETS - 2);
+  auto enqueue_group = [&](PerKey& pk, size_t g) -> int {
+    WitPipe* P = pk.pipe;
+    WitPipe::Set& b = P->set[g % WIT_SETS];
+    const size_t l0 = g * pk.G, m = std::min(pk.G, pk.jobs.size() - l0), nw = pk.key->nVars;
+    const size_t npub = pk.key->nPub;
+    HIP_TRY(host_wait(b.ev, true), "witness set reuse");  // its group of WIT_SETS groups ago
+    for (size_t j = 0; j < m; j++) {
+      const uint8_t* in = nullptr;
+      int r = get_input(pk.jobs[l0 + j], &in);
+      if (r) return r;
+      memcpy(b.pin_in + j * pk.n_in * 32, in, pk.n_in * 32);
+    }
+    if (pk.n_in)
+      HIP_TRY(hipMemcpyAsync(b.in, b.pin_in, m * pk.n_in * 32, hipMemcpyHostToDevice, P->st), "upload inputs");
+    HIP_TRY(wprog_enqueue(pk.prog, m, b.in, b.W, b.outs, b.fail, P->st), "witness group");
+    for (size_t j = 0; j < m; j++) {
+      uint8_t* o = pin_out + off[pk.jobs[l0 + j]];
+      HIP_TRY(hipMemcpyAsync(o, b.fail + j, 4, hipMemcpyDeviceToHost, P->st), "witness status");
+      if (npub) HIP_TRY(hipMemcpyAsync(o + 4, b.d + j * nw + 1, npub * 32, hipMemcpyDeviceToHost, P->st), "publics");
+    }
+    HIP_TRY(hipEventRecord(b.ev, P->st), "event");
+    return ZKFL_OK;
+  };
+  int rc = ZKFL_OK;
+  for (auto& pk : ks)
+    for (size_t g = 0; g <= ahead && g < pk.groups && rc == ZKFL_OK; g++) rc = enqueue_group(pk, g);
+  if (rc == ZKFL_OK)
+    rc = run_jobs(ctx, n, [&](size_t i, Job& J) {
+      PerKey& pk = ks[kidx[i]];
+      const size_t g = local[i] / pk.G, j = local[i] % pk.G;
+      // the key's slots hold its group g - 1 now and have drained group g - 2, whose set (mod
+      // WIT_SETS) group g + ahead takes (ahead <= WIT_SETS - 2)
+      if (j == 0 && g >= 1 && g + ahead < pk.groups) {
+        int r = enqueue_group(pk, g + ahead);
+        if (r) return r;
+      }
+      J.key = pk.key;
+      J.w = pk.pipe->set[g % WIT_SETS].d + j * pk.key->nVars;
+      J.w_ready = pk.pipe->set[g % WIT_SETS].ev;
+      J.rs = rs ? rs + 64 * i : nullptr;
+      J.proof_out = proofs_out + 256 * i;
+      return ZKFL_OK;
+    });
+  for (auto& pk : ks) {
+    const hipError_t e = hipStreamSynchronize(pk.pipe->st);
+    if (rc == ZKFL_OK && e != hipSuccess) rc = hip_fail(e, "witness pipe");
+  }
+  size_t bad = SIZE_MAX;
+  uint32_t bad_assert = 0;
+  for (size_t i = 0; rc == ZKFL_OK && i < n; i++) {
+    uint32_t f;
+    memcpy(&f, pin_out + off[i], 4);
+    if (f != 0xFFFFFFFFu) {  // unsatisfied witness: its proof bytes are zeroed
+      memset(proofs_out + 256 * i, 0, 256);
+      if (bad == SIZE_MAX) {
+        bad = i;
+        bad_assert = f;
+      }
+    }
+    uint8_t* pub = pub_of(i);
+    if (pub) memcpy(pub, pin_out + off[i] + 4, off[i + 1] - off[i] - 4);
+  }
+  (void)hipHostFree(pin_out);
+  if (rc == ZKFL_OK && bad != SIZE_MAX)
+    rc = fail(ZKFL_E_CONSTRAINT, "witness " + std::to_string(bad) + ": assert constraint #" +
+                                     std::to_string(bad_assert) + " failed (inputs do not satisfy the circuit)");
+  return rc;
+}
+}  // extern "C++"
+
+int zkfl_groth16_full_prove_batch(zkfl_ctx* ctx, zkfl_key* key, const zkfl_wprog* prog, size_t n,
+                                  const uint8_t* inputs, const uint8_t* rs, uint8_t* proofs_out, uint8_t* pubs_out) {
+  if (!ctx || (n && !proofs_out)) return fail(ZKFL_E_ARG, "full_prove: null argument");
+  size_t n_in = 0;
+  int rc = full_prove_check(ctx, key, prog, n, inputs, &n_in);
+  if (rc) return rc;
+  return full_prove_piped(
+      ctx, n, [&](size_t) { return key; }, [&](size_t) { return (const WProg*)prog->p; },
+      [&](size_t i, const uint8_t** in) {
+        *in = inputs + i * n_in * 32;
+        return ZKFL_OK;
+      },
+      rs, proofs_out, [&](size_t i) { return pubs_out ? pubs_out + (size_t)key->nPub * 32 * i : nullptr; });
+}
+
+int zkfl_groth16_full_prove_json(zkfl_ctx* ctx, zkfl_key* key, const zkfl_wprog* prog, const char* input_json,
+                                 const uint8_t* rs, uint8_t proof_out[256], uint8_t* pub_out) {
+  if (!ctx || !key || !prog || !input_json || !proof_out) return fail(ZKFL_E_ARG, "full_prove_json: null argument");
+  std::vector<uint32_t> v;
+  std::string err;
+  int rc = wprog_inputs_json(prog->p, input_json, v, err);  // the loaded program's signal table
+  if (rc) return fail(rc, err);
+  v.resize(v.size() + 8);  // never empty (a circuit without inputs still proves one witness)
+  return zkfl_groth16_full_prove_batch(ctx, key, prog, 1, reinterpret_cast<const uint8_t*>(v.data()), rs, proof_out,
+                                       pub_out);
+}
+
+// input.json texts -> input vectors on host worker threads, ahead of the slot scheduler that
+// consumes them (at most AHEAD parsed vectors held), so parsing overlaps the proofs in flight.
+namespace {
+struct JsonParsePool {
+  static constexpr size_t AHEAD = 64;
+  const WProg* prog;
+  const char* const* texts;
+  size_t n, n_in;
+  std::vector<std::vector<uint32_t>> vec;
+  std::vector<std::string> err;
+  std::vector<int> rc;
+  std::vector<uint8_t> done;
+  std::atomic<size_t> next{0};
+  size_t consumed = 0;
+  bool stop = false;
+  std::mutex mu;
+  std::condition_variable cv;
+  std::vector<std::thread> th;
+
+  JsonParsePool(const WProg* p, const char* const* t, size_t count, size_t nin)
+      : prog(p), texts(t), n(count), n_in(nin), vec(count), err(count), rc(count, 0), done(count, 0) {
+    const unsigned hw = std::max(2u, std::thread::hardware_concurrency());
+    const size_t workers = std::min<size_t>({count, (size_t)hw / 2, 8});
+    for (size_t w = 0; w < workers; w++) th.emplace_back([this] { work(); });
+  }
+  ~JsonParsePool() {
+    {
+      std::lock_guard<std::mutex> g(mu);
+      stop = true;
+    }
+    cv.notify_all();
+    for (auto& t : th) t.join();
+  }
+  void work() {
+    for (;;) {
+      const size_t i = next.fetch_add(1);
+      if (i >= n) return;
+      {
+        std::unique_lock<std::mutex> g(mu);
+        cv.wait(g, [&] { return stop || i < consumed + AHEAD; });
+        if (stop) return;
+      }
+      std::vector<uint32_t> v;
+      std::string e;
+      int r = texts[i] ? wprog_inputs_json(prog, texts[i], v, e) : ZKFL_E_ARG;
+      if (!texts[i]) e = "null input json";
+      if (r == ZKFL_OK && v.size() != n_in * 8) {
+        r = ZKFL_E_ARG;
+        e = "input json does not fill the program's inputs";
+      }
+      v.resize(n_in * 8 + 8);  // never empty
+      {
+        std::lock_guard<std::mutex> g(mu);
+        vec[i] = std::move(v);
+        err[i] = std::move(e);
+        rc[i] = r;
+        done[i] = 1;
+      }
+      cv.notify_all();
+    }
+  }
+  // Job i's vector (blocks until parsed); job i-1's vector is released (its slot copied it).
+  int get(size_t i, const uint8_t** out) {
+    std::unique_lock<std::mutex> g(mu);
+    if (i > 0) std::vector<uint32_t>().swap(vec[i - 1]);
+    consumed = i;
+    cv.notify_all();
+    cv.wait(g, [&] { return done[i] != 0; });
+    if (rc[i]) return fail(rc[i], "input " + std::to_string(i) + ": " + err[i]);
+    *out = reinterpret_cast<const uint8_t*>(vec[i].data());
+    return ZKFL_OK;
+  }
+};
+}  // namespace
+
+int zkfl_groth16_full_prove_json_batch(zkfl_ctx* ctx, zkfl_key* key, const zkfl_wprog* prog, size_t n,
+                                       const char* const* input_jsons, const uint8_t* rs, uint8_t* proofs_out,
+                                       uint8_t* pubs_out) {
+  if (!ctx || (n && (!input_jsons || !proofs_out))) return fail(ZKFL_E_ARG, "full_prove_json_batch: null argument");
+  size_t n_in = 0;
+  int rc = full_prove_check(ctx, key, prog, 0, nullptr, &n_in);
+  if (rc || n == 0) return rc;
+  JsonParsePool pool(prog->p, input_jsons, n, n_in);
+  // parsed values are < r by construction
+  return full_prove_piped(
+      ctx, n, [&](size_t) { return key; }, [&](size_t) { return (const WProg*)prog->p; },
+      [&](size_t i, const uint8_t** in) { return pool.get(i, in); }, rs, proofs_out,
+      [&](size_t i) { return pubs_out ? pubs_out + (size_t)key->nPub * 32 * i : nullptr; });
+}
+
+int zkfl_groth16_full_prove_multi(zkfl_ctx* ctx, size_t n, zkfl_key* const* keys, const zkfl_wprog* const* progs,
+                                  const uint8_t* const* inputs, const uint8_t* rs, uint8_t* proofs_out,
+                                  uint8_t* const* pubs_out) {
+  if (!ctx || (n && (!keys || !progs || !inputs || !proofs_out))) return fail(ZKFL_E_ARG, "full_prove_multi: null argument");
+  std::vector<size_t> n_in(n);
+  for (size_t i = 0; i < n; i++) {
+    int rc = full_prove_check(ctx, keys[i], progs[i], 1, inputs[i], &n_in[i]);
+    if (rc) return fail(rc, "job " + std::to_string(i) + ": " + zkfl_last_error());
+  }
+  std::vector<std::pair<const zkfl_key*, const zkfl_wprog*>> kp;  // a key's jobs share its witness program
+  for (size_t i = 0; i < n; i++) {
+    size_t c = 0;
+    while (c < kp.size() && kp[c].first != keys[i]) c++;
+    if (c == kp.size()) kp.push_back({keys[i], progs[i]});
+    else if (kp[c].second != progs[i])
+      return fail(ZKFL_E_ARG, "full_prove_multi: job " + std::to_string(i) +
+                                  " uses its key with another witness program than an earlier job");
+  }
+  return full_prove_piped(
+      ctx, n, [&](size_t i) { return keys[i]; }, [&](size_t i) { return (const WProg*)progs[i]->p; },
+      [&](size_t i, const uint8_t** in) {
+        *in = inputs[i];
+        return ZKFL_OK;
+      },
+      rs, proofs_out, [&](size_t i) { return pubs_out ? pubs_out[i] : nullptr; });
+}
+
+int zkfl_groth16_prove(zkfl_ctx* ctx, zkfl_key* key, const uint8_t* wtns, size_t wtns_len, const uint8_t* rs,
+                       uint8_t proof_out[256], uint8_t* pub_out, size_t* npub) {
+  zkfl_witness* w = nullptr;
+  int rc = zkfl_witness_upload(ctx, key, wtns, wtns_len, &w);
+  if (rc) return rc;
+  rc = zkfl_groth16_prove_resident(ctx, key, w, rs, proof_out);
+  if (rc == ZKFL_OK) {
+    if (pub_out) memcpy(pub_out, w->pub.data(), w->pub.size());
+    if (npub) *npub = key->nPub;
+  }
+  zkfl_witness_free(w);
+  return rc;
+}
+
+int zkfl_debug_prove_parts(zkfl_ctx* ctx, zkfl_key* key, const uint8_t* wtns, size_t wtns_len, uint8_t* h_out,
+                           uint8_t* msm_out) {
+  zkfl_witness* w = nullptr;
+  int rc = zkfl_witness_upload(ctx, key, wtns, wtns_len, &w);
+  if (rc) return rc;
+  ProofSlot* s = nullptr;
+  rc = get_slot(key, 0, &s);
+  uint32_t zeros[16] = {0};
+  if (rc == ZKFL_OK && !key->dbg_zero) {  // see zkfl_key::dbg_zero
+    const size_t bytes = std::max<size_t>(key->nVars, (size_t)key->n + 4) * 32;
+    hipError_t e = hipMalloc(&key->dbg_zero, bytes);
+    // on the slot's stream and waited for: hipMemset is asynchronous to the host and runs on the
+    // null stream, which the slots' non-blocking streams do not wait for -- the MSMs below read
+    // the zeros, and a recycled allocation (a freed key's memory) is not zero.  (Found as a
+    // parity failure that appeared only after earlier tests had freed large keys.)
+    if (e == hipSuccess) e = hipMemsetAsync(key->dbg_zero, 0, bytes, s->st_main);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->st_main);
+    if (e != hipSuccess) rc = hip_fail(e, "parity hook zeros");
+  }
+  if (rc == ZKFL_OK && s->busy) rc = wait_slot(s);
+  if (rc == ZKFL_OK) {
+    s->out_proof = nullptr;
+    s->out_part = nullptr;
+    rc = enqueue_proof(ctx, key, s, w->d, zeros, 1);
+  }
+  if (rc == ZKFL_OK) rc = wait_slot(s);
+  hipStream_t st = s ? s->st_main : ctx->st;
+  uint32_t* d_o = nullptr;
+  if (rc == ZKFL_OK && msm_out) {
+    hipError_t e = hipMalloc(&d_o, 64 * 4 + 128);
+    if (e == hipSuccess) {
+      point_out(st, s->res, 4, d_o);
+      point_out(st, s->resB2, 1, d_o + 64);
+      e = hipGetLastError();
+    }
+    std::vector<uint8_t> tmp(64 * 4 + 128);
+    if (e == hipSuccess) e = hipMemcpyAsync(tmp.data(), d_o, tmp.size(), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = hip_fail(e, "debug parts");
+    if (rc == ZKFL_OK) {
+      // res order A, B1, C, H ; output order A | B1 | B2 | C | H
+      memcpy(msm_out, tmp.data(), 64);
+      memcpy(msm_out + 64, tmp.data() + 64, 64);
+      memcpy(msm_out + 128, tmp.data() + 256, 128);
+      memcpy(msm_out + 256, tmp.data() + 128, 64);
+      memcpy(msm_out + 320, tmp.data() + 192, 64);
+    }
+  }
+  if (rc == ZKFL_OK && h_out) {
+    hipError_t e = hipMemcpyAsync(h_out, s->h, (size_t)key->n * 32, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = hip_fail(e, "debug h");
+  }
+  if (d_o) (void)hipFree(d_o);
+  zkfl_witness_free(w);
+  return rc;
+}
+
+}  // extern "C"

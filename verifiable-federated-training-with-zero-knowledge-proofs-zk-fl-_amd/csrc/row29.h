@@ -1,6 +1,6 @@
 // Row-distributed 29-bit Montgomery arithmetic: one value per 16-lane row of a wave, lane j of the
 // row holding limb j of the nine 29-bit limbs (lanes 9..15 zero), over a modulus M of the 29-bit
-// engine (P29 = Fq: the assembly's GLV chains, zkfl.hip glv_row_mul; R29 = Fr: the witness engine's
+// engine (P29 = Fq: the assembly's GLV chains, assemble.hip glv_row_mul; R29 = Fr: the witness engine's
 // Poseidon rounds, witness.hip), in its Montgomery domain (2^261) and with the same integer results
 // as its one-lane products (f29_mont: the same reduction digit by digit).
 //

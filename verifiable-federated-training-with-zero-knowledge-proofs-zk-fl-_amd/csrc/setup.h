@@ -29,4 +29,7 @@ hipError_t setup_lagrange(bool g2, hipStream_t st, const uint8_t* points, int lo
 hipError_t setup_lincomb(bool g2, hipStream_t st, const uint8_t* bases, size_t n_bases, size_t n_out,
                          const uint64_t* rowptr, const uint32_t* idx, const uint8_t* coefs, uint8_t* out);
 
+// Dev ceremony: out[i] = k_i * G (the curve's generator), n affine Montgomery points.
+hipError_t setup_gen_mul(bool g2, hipStream_t st, const uint8_t* scalars, size_t n, uint8_t* out);
+
 }  // namespace zkfl

@@ -6,6 +6,7 @@
 // is ~20 M G1-equivalent scalar multiplications, ~1 s on one MI355X.
 #include "setup.h"
 
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -244,6 +245,69 @@ hipError_t lincomb_t(hipStream_t st, const uint8_t* bases, size_t n_bases, size_
   return hipStreamSynchronize(st);
 }
 
+// Dev ceremony: out[i] = k_i * G (mont affine)
+template <class F>
+__global__ void __launch_bounds__(64) k_gen_mul(const uint32_t* __restrict__ scalars, size_t n, Affine<F> gen_mont,
+                          Affine<F>* __restrict__ out) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t k[8];
+  for (int j = 0; j < 8; j++) k[j] = scalars[i * 8 + j];
+  XYZZ<F> g = xyzz_from_affine<F>(gen_mont);
+  out[i] = xyzz_to_affine<F>(xyzz_scalar_mul<F>(g, k));
+}
+
+__global__ void k_g1_gen_mont(G1Aff* out) {
+  Fq x = fp_zero<FqP>(), y = fp_zero<FqP>();
+  x.v[0] = 1;
+  y.v[0] = 2;
+  out->x = fp_to_mont(x);
+  out->y = fp_to_mont(y);
+}
+
+__global__ void k_g2_gen_mont(G2Aff* out) {
+  // snarkjs/ethereum bn128 G2 generator (std form limbs)
+  const uint32_t xc0[8] = {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu};
+  const uint32_t xc1[8] = {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u};
+  const uint32_t yc0[8] = {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u};
+  const uint32_t yc1[8] = {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u};
+  Fq a, b, c, d;
+  for (int i = 0; i < 8; i++) {
+    a.v[i] = xc0[i];
+    b.v[i] = xc1[i];
+    c.v[i] = yc0[i];
+    d.v[i] = yc1[i];
+  }
+  out->x = {fp_to_mont(a), fp_to_mont(b)};
+  out->y = {fp_to_mont(c), fp_to_mont(d)};
+}
+
+// Dev ceremony (zkfl_setup_g*_gen_mul): the generator in Montgomery form from the device, then
+// out[i] = k_i * G
+template <class F>
+hipError_t gen_mul_t(hipStream_t st, const uint8_t* scalars, size_t n, uint8_t* out) {
+  if (n == 0) return hipSuccess;
+  DevBufs b;
+  uint32_t* d_s;
+  Affine<F>*d_o, *d_g;
+  ZK_CHECK(b.alloc(&d_s, n * 32));
+  ZK_CHECK(b.alloc(&d_o, n * sizeof(Affine<F>)));
+  ZK_CHECK(b.alloc(&d_g, sizeof(Affine<F>)));
+  ZK_CHECK(hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st));
+  if constexpr (std::is_same<F, Fq2Ops>::value)
+    hipLaunchKernelGGL(k_g2_gen_mont, dim3(1), dim3(1), 0, st, d_g);
+  else
+    hipLaunchKernelGGL(k_g1_gen_mont, dim3(1), dim3(1), 0, st, d_g);
+  ZK_CHECK(hipGetLastError());
+  Affine<F> g;
+  ZK_CHECK(hipMemcpyAsync(&g, d_g, sizeof(g), hipMemcpyDeviceToHost, st));
+  ZK_CHECK(hipStreamSynchronize(st));
+  hipLaunchKernelGGL(k_gen_mul<F>, dim3(zk_grid(n, 64)), dim3(64), 0, st, d_s, n, g, d_o);
+  ZK_CHECK(hipGetLastError());
+  ZK_CHECK(hipMemcpyAsync(out, d_o, n * sizeof(Affine<F>), hipMemcpyDeviceToHost, st));
+  return hipStreamSynchronize(st);
+}
+
 }  // namespace
 
 hipError_t setup_scale(bool g2, hipStream_t st, const uint8_t* points, const uint8_t* scalars, size_t n,
@@ -259,6 +323,10 @@ hipError_t setup_lincomb(bool g2, hipStream_t st, const uint8_t* bases, size_t n
                          const uint64_t* rowptr, const uint32_t* idx, const uint8_t* coefs, uint8_t* out) {
   return g2 ? lincomb_t<Fq2Ops>(st, bases, n_bases, n_out, rowptr, idx, coefs, out)
             : lincomb_t<FqOps>(st, bases, n_bases, n_out, rowptr, idx, coefs, out);
+}
+
+hipError_t setup_gen_mul(bool g2, hipStream_t st, const uint8_t* scalars, size_t n, uint8_t* out) {
+  return g2 ? gen_mul_t<Fq2Ops>(st, scalars, n, out) : gen_mul_t<FqOps>(st, scalars, n, out);
 }
 
 }  // namespace zkfl

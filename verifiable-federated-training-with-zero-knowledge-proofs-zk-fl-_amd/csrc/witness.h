@@ -1,4 +1,5 @@
-// Host interface of the GPU witness engine (csrc/witness.hip), used by the C ABI in csrc/zkfl.hip.
+// Host interface of the GPU witness engine (csrc/witness.hip), used by the C ABI in csrc/zkfl.hip
+// and the full-prove pipe in csrc/prove.hip.
 // Replaces circom's WASM witness calculator (tests/full_system_simulation.mjs:758-767).
 #pragma once
 #include <hip/hip_runtime.h>
