@@ -207,7 +207,7 @@ def test_msm_g2_identity(gpu_ctx, n):
 @pytest.mark.parametrize("width", [14, 16])
 @pytest.mark.parametrize("case", ["zeros", "ones", "dup", "cancel", "neg", "inf_base"])
 def test_msm_g2_edge_cases(gpu_ctx, monkeypatch, case, width):
-    """G2 runs on lane pairs (csrc/field.h Fq2PairOps): the exceptional additions (P + P inside a
+    """G2 runs on lane pairs (csrc/field29.h Fq2Pair29): the exceptional additions (P + P inside a
     bucket, P + (-P), infinity bases) and a single-bucket skew must stay pair-uniform."""
     monkeypatch.setenv("ZKFL_MSM_C", str(width))
     rnd = random.Random(zlib.crc32(case.encode()))

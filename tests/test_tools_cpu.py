@@ -1,6 +1,6 @@
 """Host-side measurement tools (CPU, no device): the PMC request-size attribution
-(tools/pmc_attrib.py) on synthetic rocprofv3 databases, and the wave tracer's timeline helpers
-(tools/wtrace.py) on synthetic wave records."""
+(tools/pmc_attrib.py) on synthetic rocprofv3 databases, the wave tracer's timeline helpers (tools/wtrace.py) on
+synthetic wave records, and the kernel comparison of tools/isa_check.py on hand-written listings."""
 import json
 import os
 import sqlite3
@@ -67,3 +67,25 @@ def test_wtrace_proof_split_and_gantt():
         ("acc", 0.0, 1.5, 2), ("stitch", 2.0, 3.0, 1), ("acc", 4.0, 4.5, 1)]
     assert all(abs(x["clock_GHz"] - 2.4) < 1e-9 for x in g)
     assert wtrace.kind_name(1 | 32) == "acc_g2"
+
+
+def test_isa_check_code_diff():
+    """tools/isa_check.py diff: a kernel that only moved (other addresses, another pc-relative
+    literal) compares equal; one changed operand does not."""
+    import isa_check
+    old = ["s_load_dwordx2 s[0:1], s[4:5], 0x0                       // 000000001000: C0060002 00000000",
+           "s_getpc_b64 s[2:3]                                        // 000000001008: BE821C00",
+           "s_add_u32 s2, s2, 0x1a30                                  // 00000000100C: 8002FF02 00001A30",
+           "s_addc_u32 s3, s3, 0                                      // 000000001014: 82038003",
+           "v_add_u32_e32 v1, s6, v0                                  // 000000001018: 68020006",
+           "s_cbranch_execz 3                                         // 00000000101C: BF880003 <k+0x2c>",
+           "s_endpgm                                                  // 000000001020: BF810000"]
+    moved = [ln.replace("0000000010", "0000000470").replace("0x1a30", "0x2c4").replace("00001A30", "000002C4")
+             for ln in old]
+    assert moved != old
+    assert isa_check.code_diff(old, moved) == []
+    changed = list(moved)
+    changed[4] = changed[4].replace("v1, s6, v0", "v1, s7, v0")
+    assert isa_check.code_diff(old, changed) != []
+    # a literal that is no pc-relative address (no s_getpc_b64 before it) is compared
+    assert isa_check.code_diff(old[2:], moved[2:]) != []

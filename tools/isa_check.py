@@ -22,7 +22,11 @@ both accumulation kernels.
   * functions(so) / return_address_clobbers(lines): non-kernel functions that write s[30:31], the
     return address (the round-3 G2 ceremony hang, commit 68f6c67; see return_address_clobbers).
 
+  * code_diff(old, new) / diff_main: two builds hold the same machine code, kernel by kernel (a
+    refactor's check: same instructions up to pc-relative constant addresses, same resources).
+
     python3 tools/isa_check.py [path/to/libzkfl.so]
+    python3 tools/isa_check.py diff OLD.so NEW.so
 """
 from __future__ import annotations
 
@@ -358,7 +362,85 @@ def return_address_clobbers(lines: list[str]) -> list[str]:
     return [ln.split("//")[0].strip() for ln in lines if _RA_WRITE.match(ln)]
 
 
+_PCREL = re.compile(r"^(s_add_u32|s_addc_u32)\s+(.*),\s*\S+$")
+
+
+def _code(lines: list[str]) -> list[str]:
+    """Instruction text of a kernel for comparison: the address-and-encoding comment dropped, and
+    the literal of the s_add_u32 / s_addc_u32 pair after an s_getpc_b64 replaced by <pcrel> (the
+    pair holds the pc-relative address of a constant, which moves when a kernel changes unit)."""
+    out, pending = [], 0
+    for ln in lines:
+        text = " ".join(ln.split("//")[0].split())
+        if not text or text == "...":  # objdump's mark for the zero padding behind a section's last kernel
+            continue
+        m = _PCREL.match(text) if pending else None
+        if m:
+            text = f"{m.group(1)} {m.group(2)}, <pcrel>"
+        pending = 2 if text.startswith("s_getpc_b64") else max(pending - 1, 0)
+        out.append(text)
+    return out
+
+
+def code_diff(old: list[str], new: list[str]) -> list[str]:
+    """The first instructions at which two kernels' disassemblies differ (see _code); [] if equal."""
+    a, b = _code(old), _code(new)
+    bad = [f"#{i}: {x}  |  {y}" for i, (x, y) in enumerate(zip(a, b)) if x != y]
+    if len(a) != len(b):
+        bad.append(f"{len(a)} vs {len(b)} instructions")
+    return bad[:8]
+
+
+def kernel_copies(so: str) -> dict[str, int]:
+    """{kernel symbol: code objects of the library that hold a copy of it}."""
+    n: dict[str, int] = {}
+    for co in code_objects(so):
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(co)
+            f.flush()
+            notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", f.name], check=True,
+                                   capture_output=True, text=True).stdout
+        for block in notes.split("  - .agpr_count")[1:]:
+            name = re.search(r"\.name:\s+(\S+)", block)
+            if name:
+                n[name.group(1)] = n.get(name.group(1), 0) + 1
+    return n
+
+
+def diff_main(old_so: str, new_so: str) -> int:
+    """python3 tools/isa_check.py diff OLD.so NEW.so: every kernel of OLD is in NEW with the same
+    instructions (code_diff) and the same registers, spills, scratch and LDS; prints the kernels
+    that differ, the symbols on one side only and the copies each side carries."""
+    rc = 0
+    co, cn = kernel_copies(old_so), kernel_copies(new_so)
+    do, dn = disassemble(old_so, ""), disassemble(new_so, "")
+    ro, rn = resources(old_so, ""), resources(new_so, "")
+    for name in sorted(co):
+        if name not in cn:
+            print(f"only in OLD: {name}")
+            rc = 1
+            continue
+        bad = code_diff(do[name], dn[name])
+        if ro[name] != rn[name]:
+            bad.append(f"resources {ro[name]} vs {rn[name]}")
+        if bad:
+            rc = 1
+            print(f"DIFFERS: {name}")
+            for b in bad:
+                print("   ", b)
+    for name in sorted(set(cn) - set(co)):
+        print(f"only in NEW: {name}")
+    for name in sorted(set(co) & set(cn)):
+        if co[name] != cn[name] or cn[name] > 1:
+            print(f"copies {co[name]} -> {cn[name]}: {name}")
+    print(f"OLD: {sum(co.values())} kernel symbols, {len(co)} distinct; NEW: {sum(cn.values())} kernel symbols, "
+          f"{len(cn)} distinct; {len(set(co) & set(cn))} compared")
+    return rc
+
+
 def main() -> int:
+    if len(sys.argv) == 4 and sys.argv[1] == "diff":
+        return diff_main(sys.argv[2], sys.argv[3])
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     so = sys.argv[1] if len(sys.argv) > 1 else os.path.join(
         root, "verifiable-federated-training-with-zero-knowledge-proofs-zk-fl-_amd", "libzkfl.so")

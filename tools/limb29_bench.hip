@@ -1,5 +1,5 @@
 // Microbenchmark: Fq Montgomery multiplication in nine 29-bit limbs (R = 2^261) against the
-// 8 x 32-bit whole-asm product of the G1 MSM kernels (FqOpsLazy::mul).
+// 8 x 32-bit whole-asm product (fp_mul_asm.h) that the G1 MSM kernels used before them.
 //
 // With 29-bit limbs every 32x32 product is < 2^58 (< 2^60 for limbs < 2^30), so a column of up
 // to 18 products plus the carry fits a 64-bit accumulator: each product is ONE v_mad_u64_u32,
@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "field.h"
+#include "fp_mul_asm.h"
 using namespace zkfl;
 
 struct F29 {
@@ -128,7 +129,11 @@ __device__ __forceinline__ F29 mul29_split(const F29& a, const F29& b) {
 template <int V, class T>
 __device__ __forceinline__ T vmul(const T& x, const T& y);
 template <>
-__device__ __forceinline__ Fq vmul<0, Fq>(const Fq& x, const Fq& y) { return FqOpsLazy::mul(x, y); }
+__device__ __forceinline__ Fq vmul<0, Fq>(const Fq& x, const Fq& y) {  // values in [0, 2p): no final subtraction
+  Fq r;
+  ZK_FP_MUL_ASM(r.v, x.v, y.v, FqP::P, FqP::INV);
+  return r;
+}
 template <>
 __device__ __forceinline__ F29 vmul<1, F29>(const F29& x, const F29& y) { return mul29<false>(x, y); }
 template <>
@@ -231,7 +236,7 @@ int main() {
   hipEvent_t a, b;
   hipEventCreate(&a);
   hipEventCreate(&b);
-  const char* names[5] = {"8x32 whole-asm (FqOpsLazy::mul)", "9x29, one accumulator", "9x29, ab | mp accumulators",
+  const char* names[5] = {"8x32 whole-asm (ZK_FP_MUL_ASM)", "9x29, one accumulator", "9x29, ab | mp accumulators",
                           "9x29, 2 split accumulators", "9x29, 3 split accumulators"};
   for (int v = 0; v < 5; v++) {
     float ms = 0, lat = 0;

@@ -912,7 +912,7 @@ ZK_HD XYZZ<FqOps29> f29_add(const XYZZ<FqOps29>& p, const XYZZ<FqOps29>& q) {
 }
 
 // ---------------------------------------------------------------------------
-// G2: Fq2 on lane pairs (lane 2k + h holds component h of every value, as Fq2PairOps), each
+// G2: Fq2 on lane pairs (lane 2k + h holds component h of every value: field.h pair_half), each
 // component in 29-bit limbs.  The formulas are written against a lane policy L (the device one
 // exchanges partner components through DPP; the host one in tools/f29_check.cpp runs both lanes
 // of a pair side by side), so tests/test_field29.py checks the same code on the CPU.

@@ -15,7 +15,7 @@
 //    the Wx base expansion (~2 GB for the 2^18-constraint training circuit) free.
 //  * Signed digits in [-(2^(c-1) - 1), 2^(c-1)]; the sign is applied on the fly (f29_madd_signed).
 //  * (bucket, entry) pairs are bucket-sorted (two counting passes over the (c-1)-bit bucket
-//    number, k_msm_bin_*; zero digits dropped).  The sorted entries are cut
+//    number, msm_sort.hip k_msm_bin_*; zero digits dropped).  The sorted entries are cut
 //    into fixed chunks of L entries, one lane each, independent of bucket boundaries: every lane
 //    does exactly L additions.  A bucket run that starts and ends inside its chunk is final and
 //    written to its bucket; a run cut by a chunk edge becomes an "item" (<= 2 per chunk).
@@ -23,142 +23,29 @@
 //    what is left: a bucket spread over many chunks is summed by a shallow tree instead of one
 //    lane walking its chunks (that serial walk, not the arithmetic, used to set the MSM's latency).
 //  * Accumulation uses XYZZ + affine mixed additions (10 Fq mul for G1).
-//  * Bucket reduction sum_b (b+1) S_b: 8 buckets folded serially per lane, then 64-lane blocks
+//  * Bucket reduction sum_b (b+1) S_b: 16 buckets folded serially per lane, then 64-lane blocks
 //    (LDS suffix scan + trees); two levels for the 2^(c-1) buckets, the second writing the MSM result.
+//  * One engine: both curves compute in 29-bit limbs (field29.h: G1 a point per lane, G2 a point
+//    per lane pair).  Every per-curve choice and every tunable is in msm_api.h (MsmCurve<S> and the
+//    tuning table); the 32-bit compute types and the other measured-and-rejected forms are gone
+//    (DESIGN.md §5 keeps their measurements).
 #pragma once
 #include <algorithm>
 #include <cstring>
 
 #include "field29.h"
 #include "msm_api.h"
+#include "msm_sort.h"
 #include "wtrace.h"
 
 namespace zkfl {
 
-// Kernel occupancy per curve (measured on MI355X).  G1: the accumulation fits 128
-// VGPRs (4 waves/SIMD); its stitching/reduction kernels run at 2-3.  G2 runs on lane pairs
-// (Fq2PairOps): the accumulation 168 VGPRs (3 waves/SIMD), the tails 179-241 (2 waves/SIMD), no
-// spills; one lane per G2 point needed > 256 registers, so a single wave owned the whole SIMD
-// for the kernel's duration (measured 186 -> 208 proofs/s moving G2 to lane pairs).
-// G1 in 29-bit limbs (field29.h) needs ~140 VGPRs in the accumulation: 3 waves/SIMD without
-// spills measured 352.8 proofs/s against 342.9 at 4 waves with 17 spilled VGPRs (32-bit limbs,
-// 4 waves: 331.3).
-#ifndef MSM_G1_WAVES
-#define MSM_G1_WAVES 3
-#endif
-// G2 in 29-bit limbs: 168 VGPRs + 14 spilled at 3 waves/SIMD, 180 without spills at 2 -- equal
-// throughput (399.5 vs 400.9 proofs/s, profiles/r02_s5_ab_limb29_g2.log); 2 keeps scratch out.
-#ifndef MSM_G2_WAVES
-#define MSM_G2_WAVES 2
-#endif
-// 1: the next entry's base is loaded while the current one is added (one affine point of
-// registers); 0: loaded after it, latency hidden by the other waves only.  Without it G1 at 4
-// waves/SIMD spills 3 VGPRs instead of 19 (1.71 -> 1.65 ms per proof) and G2 fits 3 waves/SIMD
-// without spills (1.00 -> 0.955 ms per proof); measured.
-#ifndef MSM_G1_PREFETCH
-#define MSM_G1_PREFETCH 0
-#endif
-#ifndef MSM_G2_PREFETCH
-#define MSM_G2_PREFETCH 0
-#endif
-// 1: the next entry's base is fetched straight into LDS (global_load_lds_dwordx4, 4 x 16 B per
-// lane, double-buffered, 8 KB per wave) while the current one is added, so the gather latency is
-// hidden without holding the point in VGPRs (which spilled / cost occupancy: MSM_G*_PREFETCH).
-#ifndef MSM_LDS_PF
-#define MSM_LDS_PF 1
-#endif
-#ifndef MSM_G2_TAIL_WAVES
-#define MSM_G2_TAIL_WAVES 2
-#endif
-#ifndef MSM_G1_TAIL_WAVES
-#define MSM_G1_TAIL_WAVES 2
-#endif
-#ifndef MSM_G1_STITCH_WAVES
-#define MSM_G1_STITCH_WAVES MSM_G1_TAIL_WAVES
-#endif
-
-// Compute type -> storage: how the point kernels read and write the stored points.  G1 and plain
-// Fq2 hold a point per lane; Fq2PairOps holds it across a lane pair (component h of every
-// coordinate in lane 2k+h), reading and writing Affine/XYZZ<Fq2Ops> memory.
+// Compute type (MsmCurve<S>::Compute, msm_api.h) -> storage: how the point kernels read and write
+// the stored points.  G1 holds a point per lane; G2 holds it across a lane pair (component h of
+// every coordinate in lane 2k+h), reading and writing Affine/XYZZ<Fq2Ops> memory.
 // PIECES: 16-B LDS-DMA pieces of one lane's share of a base record.
 template <class F>
-struct MsmIO {
-  using S = F;
-  static constexpr int LANES = 1;
-  static constexpr int PIECES = 4;
-  static ZK_DEV Affine<F> ld_aff(const Affine<S>* p, size_t i) { return p[i]; }
-  // the 16-B piece q < 4 of this lane's share of base i, and a share rebuilt from its pieces
-  // (G1: the whole 64-B point; the LDS-DMA prefetch of k_msm_accumulate)
-  static ZK_DEV const uint4* piece(const Affine<S>* p, size_t i, int q) {
-    return reinterpret_cast<const uint4*>(p + i) + q;
-  }
-  static ZK_DEV Affine<F> from_pieces(const uint32_t (&w)[4 * PIECES]) {
-    Affine<F> a;
-    memcpy(&a, w, sizeof(a));
-    return a;
-  }
-  static ZK_DEV XYZZ<F> ld(const XYZZ<S>* p, size_t i) { return p[i]; }
-  static ZK_DEV void st(XYZZ<S>* p, size_t i, const XYZZ<F>& v) { p[i] = v; }
-};
-template <>
-struct MsmIO<Fq2PairOps> {
-  using S = Fq2Ops;
-  static constexpr int LANES = 2;
-  static constexpr int PIECES = 4;
-  static ZK_DEV Affine<Fq2PairOps> ld_aff(const Affine<S>* p, size_t i) {
-    const Fq* q = reinterpret_cast<const Fq*>(p + i);
-    const uint32_t h = pair_half();
-    return {q[h], q[2 + h]};
-  }
-  // lane 2k+h holds x.c_h, y.c_h: pieces 0, 1 = x.c_h, 2, 3 = y.c_h
-  static ZK_DEV const uint4* piece(const Affine<S>* p, size_t i, int q) {
-    return reinterpret_cast<const uint4*>(p + i) + 2 * pair_half() + (q & 1) + (q >> 1) * 4;
-  }
-  static ZK_DEV Affine<Fq2PairOps> from_pieces(const uint32_t (&w)[4 * PIECES]) {
-    Affine<Fq2PairOps> a;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      a.x.v[k] = w[k];
-      a.y.v[k] = w[8 + k];
-    }
-    return a;
-  }
-  static ZK_DEV XYZZ<Fq2PairOps> ld(const XYZZ<S>* p, size_t i) {
-    const Fq* q = reinterpret_cast<const Fq*>(p + i);
-    const uint32_t h = pair_half();
-    return {q[h], q[2 + h], q[4 + h], q[6 + h]};
-  }
-  static ZK_DEV void st(XYZZ<S>* p, size_t i, const XYZZ<Fq2PairOps>& v) {
-    Fq* q = reinterpret_cast<Fq*>(p + i);
-    const uint32_t h = pair_half();
-    q[h] = v.X;
-    q[2 + h] = v.Y;
-    q[4 + h] = v.ZZ;
-    q[6 + h] = v.ZZZ;
-  }
-};
-// G1 compute types with another arithmetic over the same storage (one lane per point).
-template <class F>
-struct MsmIOSameLayout {
-  using S = FqOps;
-  static constexpr int LANES = 1;
-  static constexpr int PIECES = 4;
-  static ZK_DEV Affine<F> ld_aff(const Affine<S>* p, size_t i) { return reinterpret_cast<const Affine<F>*>(p)[i]; }
-  static ZK_DEV const uint4* piece(const Affine<S>* p, size_t i, int q) {
-    return reinterpret_cast<const uint4*>(p + i) + q;
-  }
-  static ZK_DEV Affine<F> from_pieces(const uint32_t (&w)[4 * PIECES]) {
-    Affine<F> a;
-    memcpy(&a, w, sizeof(a));
-    return a;
-  }
-  static ZK_DEV XYZZ<F> ld(const XYZZ<S>* p, size_t i) { return reinterpret_cast<const XYZZ<F>*>(p)[i]; }
-  static ZK_DEV void st(XYZZ<S>* p, size_t i, const XYZZ<F>& v) { reinterpret_cast<XYZZ<F>*>(p)[i] = v; }
-};
-template <>
-struct MsmIO<FqOpsCompact> : MsmIOSameLayout<FqOpsCompact> {};
-template <>
-struct MsmIO<FqOpsLazy> : MsmIOSameLayout<FqOpsLazy> {};
+struct MsmIO;
 // G1 in 29-bit limbs (field29.h): the same 8 x 32-bit storage, converted on every load / store
 // (stored values < 2^256, in the 2^261 Montgomery domain)
 // (pre-packed 128-B records of nine 29-bit limbs per coordinate were measured neutral in round 5,
@@ -168,10 +55,7 @@ struct MsmIO<FqOps29> {
   using S = FqOps;
   static constexpr int LANES = 1;
   static constexpr int PIECES = 4;
-  static ZK_DEV Affine<FqOps29> ld_aff(const Affine<S>* p, size_t i) {
-    const Affine<S> a = p[i];
-    return {f29_pack(a.x.v), f29_pack(a.y.v)};
-  }
+  // the 16-B piece q < 4 of this lane's share of base i (the whole 64-B point)
   static ZK_DEV const uint4* piece(const Affine<S>* p, size_t i, int q) {
     return reinterpret_cast<const uint4*>(p + i) + q;
   }
@@ -202,22 +86,13 @@ struct MsmIO<FqOps29> {
     p[i] = a;
   }
 };
-// Compute type the MSM kernels use for a stored curve (G1: redundant [0, 2p) arithmetic with
-// the compact multiply; MSM_G1_NO_LAZY: canonical values, compact multiply).
-template <class F>
-struct MsmCompute {
-  using type = F;
-};
+// G2 on lane pairs in 29-bit limbs
 template <>
 struct MsmIO<Fq2Pair29> {
   using S = Fq2Ops;
   static constexpr int LANES = 2;
   static constexpr int PIECES = 4;
-  static ZK_DEV Affine<Fq2Pair29> ld_aff(const Affine<S>* p, size_t i) {
-    const Fq* q = reinterpret_cast<const Fq*>(p + i);
-    const uint32_t h = pair_half();
-    return {f29_pack(q[h].v), f29_pack(q[2 + h].v)};
-  }
+  // lane 2k+h holds x.c_h, y.c_h: pieces 0, 1 = x.c_h, 2, 3 = y.c_h
   static ZK_DEV const uint4* piece(const Affine<S>* p, size_t i, int q) {
     return reinterpret_cast<const uint4*>(p + i) + 2 * pair_half() + (q & 1) + (q >> 1) * 4;
   }
@@ -244,20 +119,6 @@ struct MsmIO<Fq2Pair29> {
     f29_unpack(q[6 + h].v, v.ZZZ);
   }
 };
-// MSM_G1_F29 (default): 29-bit limbs (field29.h); 0: 32-bit limbs in [0, 2p) (FqOpsLazy).
-#ifndef MSM_G1_F29
-#define MSM_G1_F29 1
-#endif
-template <>
-struct MsmCompute<FqOps> {
-#if MSM_G1_F29
-  using type = FqOps29;
-#elif !defined(MSM_G1_NO_LAZY)
-  using type = FqOpsLazy;
-#else
-  using type = FqOpsCompact;
-#endif
-};
 
 // Base coordinates (n Fq values) into the 29-bit compute types' Montgomery domain:
 // x 2^261 = fp_mul(x 2^256, 2^261 mod p)
@@ -269,18 +130,6 @@ static __global__ void __launch_bounds__(256) k_msm_to_m29(Fq* __restrict__ a, s
   for (int k = 0; k < 8; k++) c.v[k] = P29::C261[k];
   a[i] = fp_mul(a[i], c);
 }
-// MSM_G2_F29 (default): lane pairs in 29-bit limbs (Fq2Pair29); 0: 32-bit limbs (Fq2PairOps).
-#ifndef MSM_G2_F29
-#define MSM_G2_F29 1
-#endif
-template <>
-struct MsmCompute<Fq2Ops> {
-#if MSM_G2_F29
-  using type = Fq2Pair29;
-#else
-  using type = Fq2PairOps;
-#endif
-};
 
 // ---------------------------------------------------------------------------
 // Key-load-time window expansion: out[i*W + j] = 2^(c j) * in[i]  (affine)
@@ -322,252 +171,6 @@ __global__ void __launch_bounds__(64) k_msm_expand(const Affine<F>* __restrict__
 // ---------------------------------------------------------------------------
 // Per-MSM kernels
 // ---------------------------------------------------------------------------
-// Window j of a 256-bit scalar (8 x 32-bit words): bits [c j, c j + c) (j is unrolled, so the
-// word index and shifts are constants).
-template <int C>
-ZK_DEV uint32_t msm_window(const uint32_t (&s)[8], int j) {
-  const int b = C * j, w = b >> 5, sh = b & 31;
-  uint32_t x = s[w] >> sh;
-  if (sh + C > 32 && w + 1 < 8) x |= s[w + 1] << (32 - sh);
-  return x & ((1u << C) - 1u);
-}
-
-// ---------------------------------------------------------------------------
-// Bucket sort of the digits (rocPRIM's onesweep radix sort until round 2: DESIGN.md §5).
-// Keys are (c-1)-bit bucket numbers, so two counting passes put every non-zero digit in bucket
-// order with no look-back and no memsets:
-//   count   per block of bases: digits -> LDS histogram of the high key bits -> cnt[bin][block]
-//   scan    one workgroup: cnt (bin-major) -> exclusive offsets, bin starts, nnz
-//   scatter per block: digits again (the scalars are 2 B per entry, the pairs 6) -> each pair
-//           to its high bin at an LDS-atomic cursor
-//   bins    one workgroup per high bin: LDS histogram of the low bits, then each pair to its
-//           bucket at an LDS-atomic cursor
-// Zero digits are dropped (the accumulation reads only the first nnz pairs).  The order inside
-// a bucket is arbitrary: a bucket's sum does not depend on it, and the proof is affine.
-// ---------------------------------------------------------------------------
-constexpr int MSM_SORT_T = 256;           // threads per block in count / scatter
-constexpr int MSM_SORT_HB = 1 << MSM_SORT_HIGH_BITS; // high bins (every window width)
-// key bits sorted inside a high bin at window width C, and its low counters
-template <int C>
-constexpr int msm_sort_lb() {
-  return C - 1 - MSM_SORT_HIGH_BITS;
-}
-template <int C>
-constexpr int msm_sort_nl() {
-  return 1 << msm_sort_lb<C>();
-}
-constexpr int MSM_SORT_MAXBLK = 32768 / MSM_SORT_HB; // count/scatter blocks (the scan holds cnt in LDS)
-static_assert(MSM_SORT_HB <= MSM_SORT_T, "bucket sort split");
-constexpr int MSM_SORT_BT = 1024;         // threads of the scan workgroup
-constexpr int MSM_SORT_BINT = MSM_SORT_BIN_THREADS;  // threads per high-bin workgroup
-static_assert(MSM_SORT_HB * MSM_SORT_MAXBLK == 32 * MSM_SORT_BT, "scan: 32 counters per thread");
-
-// Signed digits of base i: fn(key, val) for every non-zero digit d of its scalar (window j),
-// key = |d| - 1 (the bucket), val = (i W + j) | sign << 31
-template <int C, class Fn>
-ZK_DEV void msm_for_digits(const uint32_t* __restrict__ scalars, const uint32_t* __restrict__ extra,
-                           const uint32_t* __restrict__ sidx, uint32_t extra_start, size_t i, Fn&& fn) {
-  constexpr int W = msm_w_of(C), NB = msm_nb_of(C);
-  const uint32_t si = sidx ? sidx[i] : (uint32_t)i;
-  const uint32_t* src = si < extra_start ? scalars + (size_t)si * 8 : extra + (size_t)(si - extra_start) * 8;
-  const uint4* sp = reinterpret_cast<const uint4*>(src);
-  const uint4 a = sp[0], b = sp[1];
-  const uint32_t s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  uint32_t carry = 0;
-#pragma unroll
-  for (int j = 0; j < W; j++) {
-    const uint32_t raw = msm_window<C>(s, j);
-    int32_t d = (int32_t)(raw + carry);
-    carry = d > NB ? 1u : 0u;
-    if (carry) d -= (1 << C);
-    if (d != 0) {
-      const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-      fn(mag - 1, (uint32_t)(i * W + j) | (d < 0 ? 0x80000000u : 0u));
-    }
-  }
-}
-
-// One sort of a launch (blockIdx.y): its scalars and base map, its blocking (per_blk bases per
-// count / scatter block, nblk blocks) and its scratch.  Every sort launch takes a table of up to
-// MSM_TAIL_MAX of them, so independent MSMs of a proof sort in the same four launches.
-struct MsmSortJob {
-  const uint32_t* scalars;
-  const uint32_t* extra;
-  const uint32_t* sidx;
-  uint32_t extra_start;
-  uint32_t n, per_blk, nblk;
-  uint32_t* cnt;        // [HB][nblk] counts, then exclusive offsets
-  uint32_t* bin_start;  // [HB + 1]
-  uint32_t* nnz;
-  uint16_t* keys_in;
-  uint32_t* vals_in;
-  uint16_t* keys_out;
-  uint32_t* vals_out;
-};
-struct MsmSortArgs {
-  MsmSortJob j[MSM_TAIL_MAX];
-};
-
-template <int C>
-__global__ void __launch_bounds__(MSM_SORT_T) k_msm_bin_count(const MsmSortArgs A) {
-  ZK_WT(WT_SORT_COUNT);
-  ZK_LIGHT();
-  constexpr int LB = msm_sort_lb<C>();
-  const MsmSortJob& J = A.j[blockIdx.y];
-  if (blockIdx.x >= J.nblk) return;
-  __shared__ uint32_t h[MSM_SORT_HB];
-  if (threadIdx.x < MSM_SORT_HB) h[threadIdx.x] = 0;
-  __syncthreads();
-  const size_t i0 = (size_t)blockIdx.x * J.per_blk, i1 = i0 + J.per_blk < J.n ? i0 + J.per_blk : J.n;
-  for (size_t i = i0 + threadIdx.x; i < i1; i += MSM_SORT_T)
-    msm_for_digits<C>(J.scalars, J.extra, J.sidx, J.extra_start, i,
-                      [&](uint32_t key, uint32_t) { atomicAdd(&h[key >> LB], 1u); });
-  __syncthreads();
-  if (threadIdx.x < MSM_SORT_HB) J.cnt[(size_t)threadIdx.x * J.nblk + blockIdx.x] = h[threadIdx.x];
-}
-
-// cnt[HB * nblk] (bin-major) -> exclusive offsets in place; bin_start[HB + 1]; *nnz.
-// The scan keeps all 32 K counters in LDS (~139 KB): gfx950's 160 KB per workgroup.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "the bucket sort's scan needs gfx950's 160 KB of LDS"
-#endif
-static __global__ void __launch_bounds__(MSM_SORT_BT) k_msm_bin_scan(const MsmSortArgs A) {
-  ZK_WT(WT_SORT_SCAN);
-  ZK_LIGHT();
-  const MsmSortJob& J = A.j[blockIdx.y];
-  uint32_t* __restrict__ cnt = J.cnt;
-  uint32_t* __restrict__ bin_start = J.bin_start;
-  const uint32_t nblk = J.nblk;
-  __shared__ uint32_t c[MSM_SORT_HB * MSM_SORT_MAXBLK + MSM_SORT_BT];  // +1 word per 32: no bank conflicts
-  __shared__ uint32_t part[MSM_SORT_BT];
-  const uint32_t total = MSM_SORT_HB * nblk, t = threadIdx.x;
-  for (uint32_t k = t; k < total; k += MSM_SORT_BT) c[k + (k >> 5)] = cnt[k];
-  __syncthreads();
-  uint32_t s = 0;
-  for (uint32_t q = 0; q < 32; q++) {
-    const uint32_t k = t * 32 + q;
-    if (k < total) s += c[k + (k >> 5)];
-  }
-  part[t] = s;
-  __syncthreads();
-  for (uint32_t off = 1; off < MSM_SORT_BT; off <<= 1) {
-    const uint32_t v = t >= off ? part[t - off] : 0u;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = part[t] - s;
-  for (uint32_t q = 0; q < 32; q++) {
-    const uint32_t k = t * 32 + q;
-    if (k < total) {
-      const uint32_t v = c[k + (k >> 5)];
-      c[k + (k >> 5)] = run;
-      run += v;
-    }
-  }
-  __syncthreads();
-  for (uint32_t k = t; k < total; k += MSM_SORT_BT) {
-    const uint32_t v = c[k + (k >> 5)];
-    cnt[k] = v;
-    if (k % nblk == 0) bin_start[k / nblk] = v;
-  }
-  if (t == MSM_SORT_BT - 1) {
-    bin_start[MSM_SORT_HB] = part[t];
-    *J.nnz = part[t];
-  }
-}
-
-template <int C>
-__global__ void __launch_bounds__(MSM_SORT_T) k_msm_bin_scatter(const MsmSortArgs A) {
-  ZK_WT(WT_SORT_SCATTER);
-  ZK_LIGHT();
-  constexpr int LB = msm_sort_lb<C>();
-  const MsmSortJob& J = A.j[blockIdx.y];
-  if (blockIdx.x >= J.nblk) return;
-  __shared__ uint32_t cur[MSM_SORT_HB];
-  if (threadIdx.x < MSM_SORT_HB) cur[threadIdx.x] = J.cnt[(size_t)threadIdx.x * J.nblk + blockIdx.x];
-  __syncthreads();
-  uint16_t* __restrict__ keys = J.keys_in;
-  uint32_t* __restrict__ vals = J.vals_in;
-  const size_t i0 = (size_t)blockIdx.x * J.per_blk, i1 = i0 + J.per_blk < J.n ? i0 + J.per_blk : J.n;
-  for (size_t i = i0 + threadIdx.x; i < i1; i += MSM_SORT_T)
-    msm_for_digits<C>(J.scalars, J.extra, J.sidx, J.extra_start, i, [&](uint32_t key, uint32_t val) {
-      const uint32_t p = atomicAdd(&cur[key >> LB], 1u);
-      keys[p] = (uint16_t)key;
-      vals[p] = val;
-    });
-}
-
-// One workgroup per high bin: [bin_start[b], bin_start[b+1]) of (tk, tv) -> buckets in (ko, vo).
-// BINT threads per workgroup (MSM_SORT_BINT).  A 256-thread variant for small MSMs measured
-// neutral on config 5 (1906.7 vs 1894.0 proofs/s, 3 alternations, profiles/r04_ab_c5_small_keys.log).
-template <int BINT, int NL>
-__global__ void __launch_bounds__(BINT) k_msm_bin_sort(const MsmSortArgs A) {
-  static_assert(BINT >= NL && BINT <= 1024 && NL >= 64, "bins: one thread per low counter");
-  ZK_WT(WT_SORT_BINS);
-  ZK_LIGHT();
-  const MsmSortJob& J = A.j[blockIdx.y];
-  const uint32_t* __restrict__ bin_start = J.bin_start;
-  const uint16_t* __restrict__ tk = J.keys_in;
-  const uint32_t* __restrict__ tv = J.vals_in;
-  uint16_t* __restrict__ ko = J.keys_out;
-  uint32_t* __restrict__ vo = J.vals_out;
-  __shared__ uint32_t c[NL];
-  const uint32_t b0 = bin_start[blockIdx.x], b1 = bin_start[blockIdx.x + 1], t = threadIdx.x;
-  if (b0 == b1) return;
-  if (t < NL) c[t] = 0;
-  __syncthreads();
-#if MSM_SORT_STAGE
-  // a bin that fits is read from memory once: its pairs wait in LDS for the placing loop
-  __shared__ uint16_t sk[MSM_SORT_STAGE];
-  __shared__ uint32_t sv[MSM_SORT_STAGE];
-  const bool staged = b1 - b0 <= MSM_SORT_STAGE;
-  for (uint32_t p = b0 + t; p < b1; p += BINT) {
-    const uint16_t key = tk[p];
-    if (staged) {
-      sk[p - b0] = key;
-      sv[p - b0] = tv[p];
-    }
-    atomicAdd(&c[key & (NL - 1)], 1u);
-  }
-#else
-  for (uint32_t p = b0 + t; p < b1; p += BINT) atomicAdd(&c[tk[p] & (NL - 1)], 1u);
-#endif
-  __syncthreads();
-  // exclusive scan of the low counters by the first waves (wave scan + wave totals)
-  uint32_t v = 0, x = 0;
-  if (t < NL) {
-    v = c[t];
-    x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = __shfl_up(x, o);
-      if ((t & 63) >= (uint32_t)o) x += y;
-    }
-  }
-  __shared__ uint32_t wt[NL / 64];
-  if (t < NL && (t & 63) == 63) wt[t >> 6] = x;
-  __syncthreads();
-  if (t < NL) {
-    uint32_t base = b0;
-    for (uint32_t w = 0; w < (t >> 6); w++) base += wt[w];
-    c[t] = base + x - v;
-  }
-  __syncthreads();
-  for (uint32_t p = b0 + t; p < b1; p += BINT) {
-#if MSM_SORT_STAGE
-    const uint16_t key = staged ? sk[p - b0] : tk[p];
-    const uint32_t val = staged ? sv[p - b0] : tv[p];
-#else
-    const uint16_t key = tk[p];
-    const uint32_t val = tv[p];
-#endif
-    const uint32_t q = atomicAdd(&c[key & (NL - 1)], 1u);
-    ko[q] = key;
-    vo[q] = val;
-  }
-}
-
 // Where a bucket run found by one lane goes (shared by the accumulation and stitching levels).
 // A run [a, b] of bucket k inside a lane's range [q0, q1) is open on the left if it starts the
 // range and the previous range ends in the same bucket, open on the right likewise.  A closed
@@ -610,7 +213,6 @@ ZK_DEV void msm_acc_chunk(const uint16_t* __restrict__ keys, const uint32_t* __r
                           uint32_t* __restrict__ item_key, XYZZ<S>* __restrict__ item_val,
                           XYZZ<S>* __restrict__ buckets, uint32_t target, uint32_t* __restrict__ live, size_t c) {
   using IO = MsmIO<F>;
-  constexpr bool PF = sizeof(typename S::T) == 32 ? MSM_G1_PREFETCH : MSM_G2_PREFETCH;
   const uint32_t nnz = *nnz_ptr;
   const uint32_t L = msm_chunk_len<S>(nnz, target);
   const size_t p0 = c * L;
@@ -626,7 +228,9 @@ ZK_DEV void msm_acc_chunk(const uint16_t* __restrict__ keys, const uint32_t* __r
     k1 = keys[p0 + 1];
     v1 = vals[p0 + 1];
   }
-#if MSM_LDS_PF
+  // The next entry's base is fetched straight into LDS (global_load_lds_dwordx4, 4 x 16 B per
+  // lane, double-buffered, 8 KB per wave) while the current one is added, so the gather latency is
+  // hidden without holding the point in VGPRs (a register prefetch spilled / cost occupancy).
   // lane l's piece q of buffer b lands at pf[b][q][l] (an LDS-DMA writes base + lane x 16 B).  A
   // native 4 x u32 vector type: with HIP's uint4 struct the reads below were lowered to 32
   // ds_read_u16 plus ~100 byte-reassembly instructions per entry (gfx950, ROCm 7.2)
@@ -642,11 +246,7 @@ ZK_DEV void msm_acc_chunk(const uint16_t* __restrict__ keys, const uint32_t* __r
   };
   fetch(v0 & 0x7FFFFFFFu, 0);
   uint32_t it = 0;
-#else
-  Affine<F> a = IO::ld_aff(bases, v0 & 0x7FFFFFFFu);
-#endif
   for (uint32_t p = (uint32_t)p0; p < p1; p++) {
-#if MSM_LDS_PF
     const int b = it++ & 1;
     // the LDS-DMA of this buffer must have landed: with the native vector type the compiler no
     // longer connects these reads to the global_load_lds writes and dropped the vmcnt wait on the
@@ -663,10 +263,6 @@ ZK_DEV void msm_acc_chunk(const uint16_t* __restrict__ keys, const uint32_t* __r
     }
     const Affine<F> a = IO::from_pieces(u);
     if (p + 1 < p1) fetch(v1 & 0x7FFFFFFFu, b ^ 1);
-#else
-    Affine<F> an;
-    if (PF && p + 1 < p1) an = IO::ld_aff(bases, v1 & 0x7FFFFFFFu);
-#endif
     uint32_t k2 = 0, v2 = 0;
     if (p + 2 < p1) {
       k2 = keys[p + 2];
@@ -687,10 +283,6 @@ ZK_DEV void msm_acc_chunk(const uint16_t* __restrict__ keys, const uint32_t* __r
     v0 = v1;
     v1 = v2;
     k1 = k2;
-#if !MSM_LDS_PF
-    if (PF) a = an;
-    else if (p + 1 < p1) a = IO::ld_aff(bases, v0 & 0x7FFFFFFFu);
-#endif
   }
   if (!slot0) item_key[2 * c] = (uint32_t)keys[p0] | MSM_ITEM_DUMMY;
   if (!slot1) item_key[2 * c + 1] = (uint32_t)keys[p1 - 1] | MSM_ITEM_DUMMY;
@@ -730,8 +322,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MINW)))
                    A.target[y], A.live[y], ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / MsmIO<F>::LANES);
 }
 
-}  // namespace zkfl
-namespace zkfl {
 
 // Item count of stitching level `level` (>= 1), derived on the device from nnz.
 template <class S>
@@ -865,18 +455,7 @@ __global__ void __launch_bounds__(MSM_STITCH_LAST * MsmIO<F>::LANES) k_msm_stitc
 // LDS suffix scan and two trees (depth ~18).  Level 0 reads the buckets as both a and s (g = 1,
 // Q = 8: 64 blocks); level 1 (Q = 1) combines the 64 block results into the MSM result.  Serial
 // folding first keeps the waves few: the reduction's cost is its waves' register-time.
-// Q0: buckets folded serially per lane at level 0 (per curve: the reduction's waves hold their
-// registers for the whole serial fold, but fewer, longer lanes do less scan/tree work per bucket)
-#ifndef MSM_G1_WSUM_Q
-#define MSM_G1_WSUM_Q 16
-#endif
-#ifndef MSM_G2_WSUM_Q
-#define MSM_G2_WSUM_Q 16
-#endif
-template <class S>
-constexpr int msm_wsum_q0() {
-  return sizeof(typename S::T) == 32 ? MSM_G1_WSUM_Q : MSM_G2_WSUM_Q;
-}
+// Q0: buckets folded serially per lane at level 0 (MsmCurve<S>::WSUM_Q).
 // Q0 of the latency schedule's reduction (one proof alone, msm_tails(..., fast = true)): 128
 // level-0 blocks (4 buckets per lane at c = 16, 1 at c = 14), a 128-lane level 1 -- about 45
 // dependent point operations on the chain instead of ~70, for ~1.8x the reduction's (small) work
@@ -1048,16 +627,6 @@ k_msm_wsum_joint(const MsmJointArgs<S1, S2> ja) {
 // ---------------------------------------------------------------------------
 // Host-side plan
 // ---------------------------------------------------------------------------
-// fn(std::integral_constant<int, C>) for the window width c of a base set (MSM_C or MSM_C_SMALL:
-// the widths whose kernels are instantiated)
-template <class Fn>
-hipError_t msm_with_c(int c, Fn&& fn) {
-  if (c == MSM_C) return fn(std::integral_constant<int, MSM_C>());
-  if constexpr (MSM_C_SMALL != MSM_C)
-    if (c == MSM_C_SMALL) return fn(std::integral_constant<int, MSM_C_SMALL>());
-  return hipErrorInvalidValue;
-}
-
 template <class F>
 hipError_t msm_bases_alloc(MsmBases<F>& b, size_t n, int c) {
   if (c != MSM_C && c != MSM_C_SMALL) return hipErrorInvalidValue;
@@ -1085,19 +654,15 @@ hipError_t msm_bases_set(MsmBases<F>& b, const Affine<F>* d_bases, const uint32_
     ZK_CHECK(hipMalloc(&b.sidx, b.n * sizeof(uint32_t)));
     ZK_CHECK(hipMemcpyAsync(b.sidx, h_sidx, b.n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   }
-  using FC = typename MsmCompute<F>::type;
-  const size_t m = b.n * msm_w_of(b.c);
   if (b.n)
     ZK_CHECK(msm_with_c(b.c, [&](auto cc) {
       hipLaunchKernelGGL((k_msm_expand<F, decltype(cc)::value>), dim3(zk_grid(b.n, 64)), dim3(64), 0, st, d_bases,
                          b.n, b.bases_w);
       return hipSuccess;
     }));
-  if constexpr (std::is_same<FC, FqOps29>::value || std::is_same<FC, Fq2Pair29>::value) {
-    const size_t nfq = m * (sizeof(Affine<F>) / sizeof(Fq));
-    if (nfq)
-      hipLaunchKernelGGL(k_msm_to_m29, dim3(zk_grid(nfq, 256)), dim3(256), 0, st, reinterpret_cast<Fq*>(b.bases_w), nfq);
-  }
+  const size_t nfq = b.n * msm_w_of(b.c) * (sizeof(Affine<F>) / sizeof(Fq));
+  if (nfq)
+    hipLaunchKernelGGL(k_msm_to_m29, dim3(zk_grid(nfq, 256)), dim3(256), 0, st, reinterpret_cast<Fq*>(b.bases_w), nfq);
   return hipGetLastError();
 }
 
@@ -1110,7 +675,7 @@ hipError_t msm_scratch_alloc(MsmScratch<F>& s, size_t cap, int c, hipStream_t st
   ZK_CHECK(hipMalloc(&s.keys_out, m * sizeof(uint16_t)));
   ZK_CHECK(hipMalloc(&s.vals_in, m * sizeof(uint32_t)));
   ZK_CHECK(hipMalloc(&s.vals_out, m * sizeof(uint32_t)));
-  s.sort_tmp_bytes = (MSM_SORT_HB * MSM_SORT_MAXBLK + MSM_SORT_HB + 1) * sizeof(uint32_t);
+  s.sort_tmp_bytes = MSM_SORT_TMP_WORDS * sizeof(uint32_t);
   ZK_CHECK(hipMalloc(&s.sort_tmp, s.sort_tmp_bytes));
   (void)st;
   return hipSuccess;
@@ -1128,35 +693,26 @@ void msm_scratch_free(MsmScratch<F>& s) {
 // occupancy of its 64-thread blocks x the CUs x chunks per block (0 when unknown: fixed L).
 template <class F>
 uint32_t msm_resident_chunks() {
-#if !MSM_ADAPTIVE_L
-  return 0;
-#else
   // tests: ZKFL_MSM_TARGET=<chunks> forces a small target, so small MSMs run long chunks too
   if (const char* e = getenv("ZKFL_MSM_TARGET")) return (uint32_t)strtoul(e, nullptr, 10);
-  using FC = typename MsmCompute<F>::type;
-  constexpr int AW = sizeof(typename F::T) == 32 ? MSM_G1_WAVES : MSM_G2_WAVES;
+  using FC = typename MsmCurve<F>::Compute;
+  constexpr int AW = MsmCurve<F>::ACC_WAVES;
   int dev = 0, ncu = 0, nb = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_msm_accumulate<FC, AW>, 64, 0) != hipSuccess) return 0;
   if (ncu <= 0 || nb <= 0) return 0;
-  const uint32_t t = (uint32_t)ncu * (uint32_t)nb * (64u / MsmIO<FC>::LANES);
-  // A/B knob: ZKFL_MSM_TARGET_SCALE=<x> resizes the target (x < 1: longer chunks, fewer items)
-  if (const char* e = getenv("ZKFL_MSM_TARGET_SCALE")) return std::max<uint32_t>(64, (uint32_t)(t * atof(e)));
-  return t;
-#endif
+  return (uint32_t)ncu * (uint32_t)nb * (64u / MsmIO<FC>::LANES);
 }
 
-// Minimum entries per accumulation lane for an MSM of `cap` bases.  Small MSMs (<= 2^16 bases:
-// config 5's keys) are latency-bound chains, so they take short chunks: a shorter serial walk
-// per lane for a few more stitching items (config 5 1970 vs 1893 proofs/s at 8 vs 16, same box,
-// DESIGN.md §12).  ZKFL_MSM_L0 / ZKFL_MSM_L0_SMALL override (A/B knobs).
+// Minimum entries per accumulation lane for an MSM of `cap` bases: MSM_SMALL_L for small MSMs
+// (<= 2^16 bases), the curve's L otherwise.  It travels in bits 24-31 of the kernels' target
+// argument (msm_target_arg).
 template <class F>
 uint32_t msm_tail_l0(size_t cap) {
-  const bool small = cap <= ((size_t)1 << 16);
-  const char* e = getenv(small ? "ZKFL_MSM_L0_SMALL" : "ZKFL_MSM_L0");
-  const uint32_t l = e ? (uint32_t)atoi(e) : (small ? MSM_SMALL_L : (uint32_t)MsmChunk<F>::L);
-  return l < 1 ? 1u : l > 255 ? 255u : l;
+  static_assert(MSM_SMALL_L >= 1 && MSM_SMALL_L <= 255 && MsmCurve<F>::L >= 1 && MsmCurve<F>::L <= 255,
+                "chunk length: 8 bits of the target argument");
+  return cap <= ((size_t)1 << 16) ? (uint32_t)MSM_SMALL_L : (uint32_t)MsmCurve<F>::L;
 }
 
 template <class F>
@@ -1246,14 +802,11 @@ hipError_t msm_sort_multi(const MsmBases<F>* const* b, MsmScratch<F>* const* pl,
     if (m == 0) {  // nothing to sort: nnz = 0 (the tail reset left it so)
       continue;
     }
-    // count / scan / scatter / bins (see k_msm_bin_count); keys_in/vals_in hold the high-bin order
-    const size_t per_blk = (m + MSM_SORT_MAXBLK - 1) / MSM_SORT_MAXBLK < MSM_SORT_T
-                               ? (size_t)MSM_SORT_T
-                               : ((m + MSM_SORT_MAXBLK - 1) / MSM_SORT_MAXBLK + MSM_SORT_T - 1) / MSM_SORT_T * MSM_SORT_T;
-    const uint32_t nblk = (uint32_t)((m + per_blk - 1) / per_blk);
-    if (nblk > MSM_SORT_MAXBLK) return hipErrorInvalidValue;
+    // keys_in/vals_in hold the high-bin order (msm_sort.hip)
+    uint32_t per_blk, nblk;
+    if (!msm_sort_blocking(m, per_blk, nblk)) return hipErrorInvalidValue;
     MsmSortJob& J = A.j[ny++];
-    J = {sc[i], ex[i], b[i]->sidx, b[i]->extra_start, (uint32_t)m, (uint32_t)per_blk, nblk,
+    J = {sc[i], ex[i], b[i]->sidx, b[i]->extra_start, (uint32_t)m, per_blk, nblk,
          static_cast<uint32_t*>(pl[i]->sort_tmp), static_cast<uint32_t*>(pl[i]->sort_tmp) + MSM_SORT_HB * MSM_SORT_MAXBLK,
          nnz[i], pl[i]->keys_in, pl[i]->vals_in, pl[i]->keys_out, pl[i]->vals_out};
     gx = std::max(gx, nblk);
@@ -1261,18 +814,7 @@ hipError_t msm_sort_multi(const MsmBases<F>* const* b, MsmScratch<F>* const* pl,
     pl[i]->ko_sorted = 1;
   }
   if (ny == 0) return hipSuccess;
-  return msm_with_c(c, [&](auto cc) {
-    constexpr int C = decltype(cc)::value;
-    constexpr int NL = msm_sort_nl<C>();
-    static_assert(NL >= 64 && NL <= 1024 && MSM_SORT_BINT >= NL, "bins: one thread per low counter");
-    hipLaunchKernelGGL((k_msm_bin_count<C>), dim3(gx, ny), dim3(MSM_SORT_T), 0, st, A);
-    hipLaunchKernelGGL(k_msm_bin_scan, dim3(1, ny), dim3(MSM_SORT_BT), 0, st, A);
-    if (!(ZK_KNOCKOUT & 2) || !sorted) {  // knock-out: an MSM's own scratch keeps its first sort
-      hipLaunchKernelGGL((k_msm_bin_scatter<C>), dim3(gx, ny), dim3(MSM_SORT_T), 0, st, A);
-      hipLaunchKernelGGL((k_msm_bin_sort<MSM_SORT_BINT, NL>), dim3(MSM_SORT_HB, ny), dim3(MSM_SORT_BINT), 0, st, A);
-    }
-    return hipGetLastError();
-  });
+  return msm_sort_launch(A, gx, ny, c, sorted, st);
 }
 
 template <class F>
@@ -1296,14 +838,11 @@ hipError_t msm_accumulate_sorted(const MsmBases<F>& b, const uint16_t* keys, con
   if (t.target) chunks = std::min<size_t>(chunks, t.target);  // lanes of msm_chunk_len(nnz, target)
   if (chunks > t.max_chunks) return hipErrorInvalidValue;
   const int pidx = prof ? prof->begin(tag, st) : -1;
-  using FC = typename MsmCompute<F>::type;
+  using FC = typename MsmCurve<F>::Compute;
   constexpr int LN = MsmIO<FC>::LANES;
-  constexpr int AW = sizeof(typename F::T) == 32 ? MSM_G1_WAVES : MSM_G2_WAVES;
-  // measurement knob: ZKFL_ACC_PAD_LDS=<bytes> reserves unused LDS per accumulation block, which
-  // lowers the number of resident waves without changing the chunking (PMC traffic attribution)
-  static const size_t pad_lds = getenv("ZKFL_ACC_PAD_LDS") ? strtoul(getenv("ZKFL_ACC_PAD_LDS"), nullptr, 10) : 0;
+  constexpr int AW = MsmCurve<F>::ACC_WAVES;
   if (!((ZK_KNOCKOUT & 64) && LN == 1))
-    hipLaunchKernelGGL((k_msm_accumulate<FC, AW>), dim3(zk_grid(chunks * LN, 64)), dim3(64), pad_lds, st, keys, vals,
+    hipLaunchKernelGGL((k_msm_accumulate<FC, AW>), dim3(zk_grid(chunks * LN, 64)), dim3(64), 0, st, keys, vals,
                        b.bases_w, t.nnz, t.item_key[0], t.item_val[0], t.buckets, msm_target_arg(t), t.live);
   if (prof) prof->end(pidx, st, 0.0, t.nnz);
   return hipGetLastError();
@@ -1315,9 +854,9 @@ template <class F>
 hipError_t msm_accumulate_sorted_multi(const MsmBases<F>* const* b, const uint16_t* const* keys,
                                        const uint32_t* const* vals, MsmTail<F>* const* t, int n, hipStream_t st) {
   if (n < 1 || n > MSM_TAIL_MAX) return hipErrorInvalidValue;
-  using FC = typename MsmCompute<F>::type;
+  using FC = typename MsmCurve<F>::Compute;
   constexpr int LN = MsmIO<FC>::LANES;
-  constexpr int AW = sizeof(typename F::T) == 32 ? MSM_G1_WAVES : MSM_G2_WAVES;
+  constexpr int AW = MsmCurve<F>::ACC_WAVES;
   MsmAccArgs<F> A = {};
   size_t gx = 0;
   int ny = 0;
@@ -1362,19 +901,18 @@ hipError_t msm_accumulate(const MsmBases<F>& b, MsmScratch<F>& pl, MsmTail<F>& t
 template <class F>
 hipError_t msm_stitch(MsmTail<F>* const* t, int n, hipStream_t st) {
   if (n < 1 || n > MSM_TAIL_MAX || !msm_tails_one_c(t, n)) return hipErrorInvalidValue;
-  using FC = typename MsmCompute<F>::type;
+  using FC = typename MsmCurve<F>::Compute;
   constexpr int LN = MsmIO<FC>::LANES;
-  constexpr int SW = sizeof(typename F::T) == 32 ? MSM_G1_STITCH_WAVES : MSM_G2_TAIL_WAVES;
+  constexpr int SW = MsmCurve<F>::STITCH_WAVES;
   const MsmTailArgs<F> ta = msm_tail_args<F>(t, nullptr, n);
   size_t N = 0;
   for (int i = 0; i < n; i++) N = std::max(N, t[i]->item_cap[0]);
   N = std::max<size_t>(N, 2);
   int cur = 0;
-  static const bool last_kernel = !getenv("ZKFL_STITCH_LAST") || atoi(getenv("ZKFL_STITCH_LAST")) != 0;
   for (int level = 1; !(ZK_KNOCKOUT & 8); level++) {
     if (level >= MSM_LIVE_LEVELS) return hipErrorInvalidValue;  // liveness flags per level
     const size_t lanes = (N + MSM_SG - 1) / MSM_SG;
-    if (last_kernel && lanes <= (size_t)MSM_STITCH_LAST) {  // the remaining levels in one workgroup
+    if (lanes <= (size_t)MSM_STITCH_LAST) {  // the remaining levels in one workgroup
       hipLaunchKernelGGL((k_msm_stitch_last<FC, SW>), dim3(1, n), dim3(MSM_STITCH_LAST * LN), 0, st, ta, level, cur);
       break;
     }
@@ -1391,12 +929,12 @@ template <class F>
 hipError_t msm_wsum(const MsmTailArgs<F>& ta, int n, hipStream_t st, bool fast) {
   if (n < 1 || n > MSM_TAIL_MAX) return hipErrorInvalidValue;
   if (ZK_KNOCKOUT & 16) return hipGetLastError();
-  using FC = typename MsmCompute<F>::type;
+  using FC = typename MsmCurve<F>::Compute;
   constexpr int LN = MsmIO<FC>::LANES;
-  constexpr int TW = sizeof(typename F::T) == 32 ? MSM_G1_TAIL_WAVES : MSM_G2_TAIL_WAVES;
+  constexpr int TW = MsmCurve<F>::TAIL_WAVES;
   return msm_with_c(ta.c, [&](auto cc) {
     constexpr int C = decltype(cc)::value, NB = msm_nb_of(C);
-    constexpr int Q0 = msm_wsum_q0<F>(), QF = msm_wsum_q_fast<C>();
+    constexpr int Q0 = MsmCurve<F>::WSUM_Q, QF = msm_wsum_q_fast<C>();
     if (fast) {
       hipLaunchKernelGGL((k_msm_wsum<FC, TW, true, QF, C>), dim3(NB / (MSM_RB * QF), n), dim3(MSM_RB * LN), 0, st, ta);
       hipLaunchKernelGGL((k_msm_wsum<FC, TW, false, QF, C>), dim3(1, n), dim3(msm_wsum_rb<false, QF, C>() * LN), 0, st,
@@ -1426,10 +964,10 @@ hipError_t msm_tails_joint(MsmTail<S1>* const* t1, XYZZ<S1>* const* o1, int n1, 
   if (n1 < 1 || n1 > MSM_TAIL_MAX || n2 < 1 || n2 > MSM_TAIL_MAX || !msm_tails_one_c(t1, n1) ||
       !msm_tails_one_c(t2, n2) || t1[0]->c != t2[0]->c)
     return hipErrorInvalidValue;
-  using F1 = typename MsmCompute<S1>::type;
-  using F2 = typename MsmCompute<S2>::type;
-  static_assert(msm_wsum_q0<S1>() == msm_wsum_q0<S2>(), "joint reduction: one fold per curve");
-  constexpr int W = MSM_G1_TAIL_WAVES < MSM_G2_TAIL_WAVES ? MSM_G1_TAIL_WAVES : MSM_G2_TAIL_WAVES;
+  using F1 = typename MsmCurve<S1>::Compute;
+  using F2 = typename MsmCurve<S2>::Compute;
+  static_assert(MsmCurve<S1>::WSUM_Q == MsmCurve<S2>::WSUM_Q, "joint reduction: one fold for both curves");
+  constexpr int W = std::min(MsmCurve<S1>::TAIL_WAVES, MsmCurve<S2>::TAIL_WAVES);
   constexpr int L1 = MsmIO<F1>::LANES, L2 = MsmIO<F2>::LANES;
   static_assert(L1 == 1 && L2 == 2, "joint tails: G1 lanes, G2 lane pairs");
   MsmJointArgs<S1, S2> ja;
@@ -1458,7 +996,7 @@ hipError_t msm_tails_joint(MsmTail<S1>* const* t1, XYZZ<S1>* const* o1, int n1, 
   if (ZK_KNOCKOUT & 16) return hipGetLastError();
   return msm_with_c(t1[0]->c, [&](auto cc) {
     constexpr int C = decltype(cc)::value, NB = msm_nb_of(C);
-    constexpr int Q0 = msm_wsum_q0<S1>(), QF = msm_wsum_q_fast<C>();
+    constexpr int Q0 = MsmCurve<S1>::WSUM_Q, QF = msm_wsum_q_fast<C>();
     if (fast) {
       hipLaunchKernelGGL((k_msm_wsum_joint<F1, F2, W, true, QF, C>), dim3(NB / (MSM_RB * QF), ny),
                          dim3(2 * msm_wsum_rb<true, QF, C>()), 0, st, ja);

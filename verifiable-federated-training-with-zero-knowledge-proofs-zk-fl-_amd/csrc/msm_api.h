@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "curve.h"
@@ -23,17 +24,59 @@ namespace zkfl {
 // vs 16 bits, the metric key 388 vs 427 -- profiles/r05_ab_window_bits.log).  17 bits (15 windows,
 // 2^16 buckets) was measured and rejected in round 5 (config 5 -11%, M within noise:
 // profiles/r05_ab_c17_c5_latency.log, r05_ab_c17_large_keys.log) and is no longer accepted.
-#ifndef MSM_WINDOW_BITS
-#define MSM_WINDOW_BITS 16
-#endif
-#ifndef MSM_WINDOW_BITS_SMALL
-#define MSM_WINDOW_BITS_SMALL 14
-#endif
-#ifndef MSM_SMALL_C_BASES
-#define MSM_SMALL_C_BASES (1 << 16)
-#endif
-constexpr int MSM_C = MSM_WINDOW_BITS;     // window bits of large keys
-constexpr int MSM_C_SMALL = MSM_WINDOW_BITS_SMALL;
+//
+// The engine's tuning table: every numeric choice, with the measurement that set it (MI355X,
+// DESIGN.md §5).  An A/B edits a value here and builds the tree (tools/build_ab.sh).
+constexpr int MSM_C = 16;                    // window bits of large keys
+constexpr int MSM_C_SMALL = 14;              // window bits of small keys
+constexpr int MSM_SMALL_C_BASES = 1 << 16;   // a key of at most this many bases is small
+// high key bits of the bucket sort (its high bins, every window width): the low c - 1 - HIGH_BITS
+// bits are sorted inside one high bin (6 at c = 14, 8 at c = 16)
+constexpr int MSM_SORT_HIGH_BITS = 7;
+// threads per high-bin workgroup of the bucket sort's bins pass.  A 256-thread variant for small
+// MSMs measured neutral on config 5 (1906.7 vs 1894.0 proofs/s, 3 alternations,
+// profiles/r04_ab_c5_small_keys.log).
+constexpr int MSM_SORT_BIN_THREADS = 1024;
+constexpr int MSM_SG = 8;                    // partial sums per lane in each stitching level
+// Minimum chunk length (sorted entries per accumulation lane) of small MSMs (<= 2^16 bases), both
+// curves.  Small MSMs (config 5's keys) are latency-bound chains, so they take short chunks: a
+// shorter serial walk per lane for a few more stitching items (config 5 1970 vs 1893 proofs/s at
+// 8 vs 16, same box).
+constexpr int MSM_SMALL_L = 8;
+
+// The per-curve choices, by storage field type S (FqOps: G1, Fq2Ops: G2).
+//   Compute      the type the point kernels compute in (field29.h), over Affine/XYZZ<S> memory
+//   ACC_WAVES    waves per SIMD the register allocator must allow the accumulation kernels
+//   STITCH_WAVES / TAIL_WAVES   the same for the stitching levels / the bucket reduction
+//   L            minimum chunk length of large MSMs (msm_chunk_len)
+//   WSUM_Q       buckets folded serially per lane at level 0 of the bucket reduction: its waves
+//                hold their registers for the whole serial fold, but fewer, longer lanes do less
+//                scan/tree work per bucket
+struct FqOps29;
+struct Fq2Pair29;
+template <class S>
+struct MsmCurve;
+// G1 in 29-bit limbs needs ~140 VGPRs in the accumulation: 3 waves/SIMD without spills measured
+// 352.8 proofs/s against 342.9 at 4 waves with 17 spilled VGPRs (32-bit limbs, 4 waves: 331.3).
+// Its stitching / reduction kernels run at 2-3 waves/SIMD.
+template <>
+struct MsmCurve<FqOps> {
+  using Compute = FqOps29;
+  static constexpr int ACC_WAVES = 3, STITCH_WAVES = 2, TAIL_WAVES = 2;
+  static constexpr int L = 16, WSUM_Q = 16;
+};
+// G2 runs on lane pairs: one lane per G2 point needed > 256 registers, so a single wave owned the
+// whole SIMD for the kernel's duration (measured 186 -> 208 proofs/s moving G2 to lane pairs).  In
+// 29-bit limbs the accumulation takes 168 VGPRs + 14 spilled at 3 waves/SIMD, 180 without spills
+// at 2 -- equal throughput (399.5 vs 400.9 proofs/s, profiles/r02_s5_ab_limb29_g2.log); 2 keeps
+// scratch out.  The tails take 179-241 VGPRs (2 waves/SIMD), no spills.
+template <>
+struct MsmCurve<Fq2Ops> {
+  using Compute = Fq2Pair29;
+  static constexpr int ACC_WAVES = 2, STITCH_WAVES = 2, TAIL_WAVES = 2;
+  static constexpr int L = 16, WSUM_Q = 16;
+};
+
 __host__ __device__ constexpr int msm_w_of(int c) { return (255 + c - 1) / c; }  // windows: 254-bit scalars + the last carry
 __host__ __device__ constexpr int msm_nb_of(int c) { return 1 << (c - 1); }     // buckets (signed digits)
 constexpr int MSM_W = msm_w_of(MSM_C);
@@ -52,60 +95,19 @@ static_assert(MSM_C >= 14 && MSM_C <= 16 && MSM_C_SMALL >= 14 && MSM_C_SMALL <= 
 #if ZK_KNOCKOUT != 0 && !defined(ZK_KNOCKOUT_AB_ONLY)
 #error "ZK_KNOCKOUT builds compute wrong proofs: timing A/B only (define ZK_KNOCKOUT_AB_ONLY to acknowledge)"
 #endif
-// high key bits of the bucket sort (its high bins, every window width): the low c - 1 - HIGH_BITS
-// bits are sorted inside one high bin (6 at c = 14, 8 at c = 16, 9 at c = 17)
-#ifndef MSM_SORT_HIGH_BITS
-#define MSM_SORT_HIGH_BITS 7
-#endif
-// pairs of one high bin staged in LDS by the bucket sort's bins pass (0: the bin is read twice)
-#ifndef MSM_SORT_STAGE
-#define MSM_SORT_STAGE 0
-#endif
-// threads per high-bin workgroup of the bucket sort's bins pass
-#ifndef MSM_SORT_BIN_THREADS
-#define MSM_SORT_BIN_THREADS 1024
-#endif
-#ifndef MSM_G1_L
-#define MSM_G1_L 16
-#endif
-#ifndef MSM_STITCH_SG
-#define MSM_STITCH_SG 8
-#endif
-constexpr int MSM_L = MSM_G1_L;            // sorted entries per accumulation lane (fixed-size chunks)
-constexpr int MSM_SG = MSM_STITCH_SG;      // partial sums per lane in each stitching level
 constexpr int MSM_RB = 64;                 // items per block (one wave) in the weighted bucket reduction
 constexpr uint32_t MSM_ITEM_DUMMY = 0x80000000u;  // stitch item flag: padding (its value is infinity)
-#ifndef MSM_G2_L
-#define MSM_G2_L 16
-#endif
-// minimum chunk length of small MSMs (<= 2^16 bases), both curves (msm_tail_l0)
-#ifndef MSM_SMALL_L
-#define MSM_SMALL_L 8
-#endif
-// Chunk length per curve (storage field type S)
-template <class S>
-struct MsmChunk {
-  static constexpr int L = MSM_L;
-};
-template <>
-struct MsmChunk<Fq2Ops> {
-  static constexpr int L = MSM_G2_L;
-};
-// 1 (default): the chunk length grows with the MSM so that one accumulation launch is ONE full
-// round of resident lanes (msm_chunk_len); 0: every MSM uses MsmChunk<S>::L (A/B builds).
-#ifndef MSM_ADAPTIVE_L
-#define MSM_ADAPTIVE_L 1
-#endif
 // Entries per accumulation lane for an MSM with nnz sorted non-zero digits: the minimum L0, or the
 // fewest that keep the lanes within `target` = the lanes the device holds at once for the
-// accumulation kernel (0: always the minimum).  The kernel argument carries both: bits 0-23 the
-// lanes, bits 24-31 the tail's minimum L0 (0: MsmChunk<S>::L) -- msm_target_arg.  A longer chunk leaves fewer chunk
+// accumulation kernel (0: always the minimum), so that one accumulation launch is ONE full round
+// of resident lanes.  The kernel argument carries both: bits 0-23 the lanes, bits 24-31 the
+// tail's minimum L0 (0: MsmCurve<S>::L) -- msm_target_arg.  A longer chunk leaves fewer chunk
 // edges inside a bucket, and every such edge costs one full point addition in the stitching;
 // the launch stays one full round of lanes, so the accumulation's own duration does not change.
 // The accumulation and the stitching levels derive the same value from nnz on the device.
 template <class S>
 __host__ __device__ inline uint32_t msm_chunk_len(uint32_t nnz, uint32_t target) {
-  const uint32_t L0 = (target >> 24) ? (target >> 24) : (uint32_t)MsmChunk<S>::L;
+  const uint32_t L0 = (target >> 24) ? (target >> 24) : (uint32_t)MsmCurve<S>::L;
   target &= 0xFFFFFFu;
   if (target == 0) return L0;
   const uint32_t l = (uint32_t)(((uint64_t)nnz + target - 1) / target);
@@ -176,6 +178,15 @@ inline int msm_pick_c(size_t n) {
     if (c == MSM_C || c == MSM_C_SMALL) return c;
   }
   return n <= (size_t)MSM_SMALL_C_BASES ? MSM_C_SMALL : MSM_C;
+}
+// fn(std::integral_constant<int, C>) for the window width c of a base set (MSM_C or MSM_C_SMALL:
+// the widths whose kernels are instantiated)
+template <class Fn>
+hipError_t msm_with_c(int c, Fn&& fn) {
+  if (c == MSM_C) return fn(std::integral_constant<int, MSM_C>());
+  if constexpr (MSM_C_SMALL != MSM_C)
+    if (c == MSM_C_SMALL) return fn(std::integral_constant<int, MSM_C_SMALL>());
+  return hipErrorInvalidValue;
 }
 
 constexpr int MSM_TAIL_MAX = 4;  // MSM tails per batched launch (the 4 G1 MSMs of a proof)

@@ -78,11 +78,12 @@ static inline hipError_t zk_wtrace_bind_tu(const WtBuf&) { return hipErrorNotSup
 #endif
 
 // binders of the instrumented translation units (poly.hip, assemble.hip, msm_g1.hip, msm_g2.hip,
-// ntt.hip, witness.hip, msm_joint.hip), called together by zkfl_debug_wtrace
+// msm_sort.hip, ntt.hip, witness.hip, msm_joint.hip), called together by zkfl_debug_wtrace
 hipError_t zk_wtrace_bind_poly(const WtBuf& b);
 hipError_t zk_wtrace_bind_asm(const WtBuf& b);
 hipError_t zk_wtrace_bind_g1(const WtBuf& b);
 hipError_t zk_wtrace_bind_g2(const WtBuf& b);
+hipError_t zk_wtrace_bind_sort(const WtBuf& b);
 hipError_t zk_wtrace_bind_ntt(const WtBuf& b);
 hipError_t zk_wtrace_bind_wit(const WtBuf& b);
 hipError_t zk_wtrace_bind_joint(const WtBuf& b);
