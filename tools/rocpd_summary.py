@@ -105,7 +105,7 @@ def _short(name):
 
 
 def breakdown(db, out, proofs=6):
-    """k_proof_start opens every proof (prove.hip enqueue_proof_body); the roofline pass is the last
+    """k_proof_start opens every proof (prove.hip start); the roofline pass is the last
     `proofs` proofs of the run, serialized on one stream."""
     c = sqlite3.connect(db)
     starts = [r[0] for r in c.execute("select start from kernels where name like '%k_proof_start%' or name like '%k_set_extra%' order by start")]

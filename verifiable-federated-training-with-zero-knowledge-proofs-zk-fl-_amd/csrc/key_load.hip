@@ -200,7 +200,7 @@ int zkey_load_parsed(zkfl_ctx* ctx, const ZkeyHost& z, size_t len, double parse_
     // B_i(tau) G1 and B_i(tau) G2 vanish together in an honest zkey; the sort is shared only when
     // the two index maps really are equal
     k->share_b = im[QB1].sidx == im[QB2].sidx && !im[QB1].sidx.empty();
-    k->front = k->share_b && nshards == 1 && logn <= 16;
+    k->front = k->share_b && nshards == 1 && logn <= ctx->opts.small_logn;
     if (e == hipSuccess) e = upload(k->bCH, im[QCH]);
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;

@@ -40,9 +40,21 @@ using namespace zkfl;
 
 struct WitPipe;  // csrc/prove.hip
 
+// The proof scheduler's options: read from the environment once, when the
+// context is created (zkfl_ctx_create), and fixed for its keys.  The defaults are the measured
+// best; each other value picks another schedule for the same proof bytes (csrc/prove.hip plan_proof).
+struct SchedOpts {
+  bool graph = true;      // ZKFL_GRAPH: graph replay of the one-stream schedules
+  bool stagger = true;    // ZKFL_STAGGER: odd slots run ABC + NTT first
+  bool lowlat = true;     // ZKFL_LOWLAT: a batch of one takes the latency schedule
+  bool fast_wsum = true;  // ZKFL_FAST_WSUM: shorter-chain bucket reduction (latency schedule, small keys)
+  int small_logn = 16;    // ZKFL_SMALL_LOGN: a key with a domain <= 2^small_logn is a small key
+};
+
 struct zkfl_ctx {
   int device = 0;
   hipStream_t st = nullptr;  // primitives, key loading, verification
+  SchedOpts opts;
   Profiler prof;
   zkfl::VkDev* vk = nullptr;       // last prepared verification key (reused while the vk bytes repeat)
   zkfl::PosTables* pos = nullptr;  // Poseidon constants of every width (first hashing call)
@@ -77,22 +89,20 @@ struct ProofSlot {
   uint32_t* d_parts = nullptr;  // [96]: this rank's part of a split proof (A'|B1'|B2'|C'|H, std affine)
   uint8_t* pinned = nullptr;    // proof (256) | r, s (64) | GLV halves (128) | witness address (8, at
                                 // W_PTR_OFF) | pad | part (768 at 512)
-  // the low-latency schedule (enqueue_proof_lowlat, one proof alone): two side streams, their
-  // events (B sorted and B1 accumulated | B2 final | T = s pi_A + r B1 final) and B's own sort
-  // scratch, so C + H can sort on the main stream while B2 still reads B's pairs; made on first use
+  // side resources (slot_side_resources): A's and B's own sort scratch, so C + H can sort in g1s
+  // while B2 still reads B's pairs -- a small key's slots hold them from the start (run_front),
+  // any other slot from its first proof alone (run_lowlat), which also makes that schedule's two
+  // side streams and their events (B sorted | B2 final | T = s pi_A + r B1 final)
   hipStream_t st_lat[2] = {nullptr, nullptr};
   hipEvent_t ev_lat[3] = {nullptr, nullptr, nullptr};
   MsmScratch<FqOps> g1s_b;
-  MsmScratch<FqOps> g1s_a;  // A's sort scratch in the overlapped schedule (A beside C + H)
-  // graph replay (default on; ZKFL_GRAPH=0 off): the one-stream proof chain captured once per witness address
-  struct Graph {
-    const Fr* w = nullptr;
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ex = nullptr;
-  };
-  std::vector<Graph> graphs;
+  MsmScratch<FqOps> g1s_a;
+  // graph replay (the context's SchedOpts::graph, ZKFL_GRAPH when it was created; default on): a
+  // slot's one-stream schedule captured once, on its second proof
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t graph_exec = nullptr;
   // the graph's witness: each graph-replayed proof first copies its witness here (nVars x 32 B,
-  // a few us of HBM time), so one graph per slot serves every witness buffer
+  // a few us of HBM time), so the slot's one graph serves every witness buffer
   Fr* w_stage = nullptr;
   uint32_t direct_proofs = 0;     // proofs this slot ran kernel by kernel (the first one: no capture)
   // B2 shares B1's digit sort, so its tail counts with B1's nnz (g2t.nnz == g1t[1].nnz, owned
@@ -126,9 +136,10 @@ struct zkfl_key {
   // so the key holds no separate C and H bases (they were ~0.5 GB of expanded bases per key at 2^18)
   Fr* dbg_zero = nullptr;
   bool share_b = false;  // B1 and B2 have the same base index map: one digit sort serves both
-  // small keys (domain <= 2^16, config 5's circuits): a proof sorts A, B1 and C + H in the same four
-  // launches and accumulates them in one (msm_sort_multi / msm_accumulate_sorted_multi), after ABC /
-  // NTT; the slots hold A's and B's sort scratch for it (g1s_a, g1s_b)
+  // small keys (domain <= 2^SchedOpts::small_logn, config 5's circuits): a proof sorts A, B1 and
+  // C + H in the same four launches and accumulates them in one (msm_sort_multi /
+  // msm_accumulate_sorted_multi), after ABC / NTT; the slots hold A's and B's sort scratch for it
+  // (g1s_a, g1s_b)
   bool front = false;
   int msm_c = MSM_C;     // window bits of every base set of the key (msm_pick_c of its largest)
   NttPlan ntt;

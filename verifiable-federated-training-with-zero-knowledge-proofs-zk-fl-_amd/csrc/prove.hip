@@ -1,8 +1,9 @@
 // The proof scheduler and the prove entry points: a key's proof slots (stream, scratch, MSM tails),
-// the chain a proof runs on its slot (enqueue_proof_body; enqueue_proof_lowlat for one proof alone;
-// graph replay), the batch scheduler behind every prove call (run_jobs) and the batched full-prove
-// pipe with its witness groups and JSON parse pool (full_prove_piped).  The kernels it launches
-// live in poly.hip, assemble.hip, ntt.hip and the MSM units.
+// the plan of a proof (plan_proof: decided once, from the context's SchedOpts) and the schedule it
+// picks on its slot (run_lowlat for one proof alone, run_front for small keys, run_chain; the last
+// two replayed from a graph), the batch scheduler behind every prove call (run_jobs) and the
+// batched full-prove pipe with its witness groups and JSON parse pool (full_prove_piped).  The
+// kernels it launches live in poly.hip, assemble.hip, ntt.hip and the MSM units.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -12,7 +13,6 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
-#include <cstdlib>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -34,40 +34,6 @@ constexpr size_t W_PTR_OFF = 448;  // pinned: the graph-replayed proof's witness
 // the proof's 256 bytes go straight into the slot's pinned buffer (k_assemble*)
 inline uint32_t* proof_out(ProofSlot* s) { return reinterpret_cast<uint32_t*>(s->pinned); }
 
-void slot_release(ProofSlot* s) {
-  if (!s) return;
-  if (s->st_main) (void)hipStreamSynchronize(s->st_main);
-  if (s->nnz_alias) s->g2t.nnz = nullptr;
-  msm_scratch_free(s->g1s);
-#if ZK_KNOCKOUT & 2
-  for (MsmScratch<FqOps>& x : s->g1s_ko) msm_scratch_free(x);
-#endif
-  for (auto& t : s->g1t) msm_tail_free(t);
-  msm_scratch_free(s->g2s);
-  msm_tail_free(s->g2t);
-  void* ptrs[] = {s->abc, s->abc_head, s->abc_tail, s->h, s->res, s->resB2, s->d_rs, s->d_parts,
-                  s->w_stage};  // extra lives in h
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (s->pinned) (void)hipHostFree(s->pinned);
-  for (hipStream_t st : s->st_lat)
-    if (st) (void)hipStreamSynchronize(st);
-  msm_scratch_free(s->g1s_b);
-  msm_scratch_free(s->g1s_a);
-  for (auto& gr : s->graphs) {
-    if (gr.ex) (void)hipGraphExecDestroy(gr.ex);
-    if (gr.g) (void)hipGraphDestroy(gr.g);
-  }
-  s->graphs.clear();
-  for (hipEvent_t e : {s->ev_done, s->ev_lat[0], s->ev_lat[1], s->ev_lat[2]})
-    if (e) (void)hipEventDestroy(e);
-  for (hipStream_t st : {s->st_main, s->st_lat[0], s->st_lat[1]})
-    if (st) (void)hipStreamDestroy(st);
-  delete s;
-}
-
-int graph_mode();
-
 // Release a slot's latency-schedule streams and events (made again on its next batch of one).
 void slot_drop_lowlat(ProofSlot* s) {
   for (hipStream_t& st : s->st_lat)
@@ -81,6 +47,47 @@ void slot_drop_lowlat(ProofSlot* s) {
       (void)hipEventDestroy(e);
       e = nullptr;
     }
+}
+
+void slot_release(ProofSlot* s) {
+  if (!s) return;
+  if (s->st_main) (void)hipStreamSynchronize(s->st_main);
+  slot_drop_lowlat(s);
+  if (s->nnz_alias) s->g2t.nnz = nullptr;
+  msm_scratch_free(s->g1s);
+#if ZK_KNOCKOUT & 2
+  for (MsmScratch<FqOps>& x : s->g1s_ko) msm_scratch_free(x);
+#endif
+  for (auto& t : s->g1t) msm_tail_free(t);
+  msm_scratch_free(s->g2s);
+  msm_tail_free(s->g2t);
+  void* ptrs[] = {s->abc, s->abc_head, s->abc_tail, s->h, s->res, s->resB2, s->d_rs, s->d_parts,
+                  s->w_stage};  // extra lives in h
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  if (s->pinned) (void)hipHostFree(s->pinned);
+  msm_scratch_free(s->g1s_b);
+  msm_scratch_free(s->g1s_a);
+  if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
+  if (s->graph) (void)hipGraphDestroy(s->graph);
+  if (s->ev_done) (void)hipEventDestroy(s->ev_done);
+  if (s->st_main) (void)hipStreamDestroy(s->st_main);
+  delete s;
+}
+
+// A slot's side resources (ProofSlot::g1s_a): A's and B's own sort scratch and, for the latency
+// schedule (need_streams), its two side streams and their three events.  What the slot holds
+// already is kept.  slot_release frees all of them, slot_drop_lowlat the streams and events.
+hipError_t slot_side_resources(ProofSlot* s, const zkfl_key* k, bool need_streams) {
+  if (need_streams) {
+    for (hipStream_t& st : s->st_lat)
+      if (!st) ZK_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    for (hipEvent_t& e : s->ev_lat)
+      if (!e) ZK_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  if (!s->g1s_a.keys_out) ZK_CHECK(msm_scratch_alloc(s->g1s_a, k->bA.n, k->msm_c, k->ctx->st));
+  if (!s->g1s_b.keys_out) ZK_CHECK(msm_scratch_alloc(s->g1s_b, k->bB1.n, k->msm_c, k->ctx->st));
+  return hipSuccess;
 }
 
 hipError_t slot_create(zkfl_key* k, ProofSlot** out) {
@@ -113,11 +120,8 @@ hipError_t slot_create(zkfl_key* k, ProofSlot** out) {
     s->g2t.nnz = s->g1t[1].nnz;
     s->nnz_alias = true;
   }
-  if (graph_mode()) ZK_CHECK(hipMalloc(&s->w_stage, nV * 32));
-  if (k->front) {  // A's and B's own sort scratch (C + H sorts in g1s)
-    ZK_CHECK(msm_scratch_alloc(s->g1s_a, k->bA.n, c, st));
-    ZK_CHECK(msm_scratch_alloc(s->g1s_b, k->bB1.n, c, st));
-  }
+  if (k->ctx->opts.graph) ZK_CHECK(hipMalloc(&s->w_stage, nV * 32));
+  if (k->front) ZK_CHECK(slot_side_resources(s, k, false));  // run_front: C + H sorts in g1s
   ZK_CHECK(hipMalloc(&s->h, (n + 4) * 32));   // h, then the extra slots (the merged C+H MSM's scalars)
   s->extra = s->h + n;
   ZK_CHECK(hipMalloc(&s->abc, n * 3 * 32));
@@ -251,15 +255,108 @@ int get_rs(const uint8_t* rs, uint32_t out[16]) {
   return ZKFL_OK;
 }
 
-// Enqueue one proof on a slot (asynchronous), a serial chain on the slot's one stream:
-//   r, s + GLV halves, scalar vectors, accumulate A, B1, B2 (B1's sort) and its tail, ABC, coset
-//   NTT x3, join, accumulate C + H, the G1 tails as one batch, assembly (pi_a, pi_b, pi_c) [ev_done]
-// plain = 1 (parity hook): alpha/beta/delta/r/s terms zeroed, nothing assembled.
-// plain = 2 (split proof): the full augmentation (on shard 0's bases), no assembly; the part
-// A' | B1' | B2' | C' + H | infinity goes to pinned + 512 (zkfl_groth16_prove_part_batch).
-// ABC (a, b, c on the domain), the coset NTT of all three and h = a b - c (std form: the H MSM's
-// scalars) for one proof on stream st.
-int enqueue_abc_ntt(zkfl_key* k, ProofSlot* s, const Fr* d_w, hipStream_t st, Profiler* prof) {
+// What a proof is run for.
+enum class ProofMode {
+  Proof,      // a whole proof: its 256 bytes assembled into the slot's pinned buffer
+  Parts,      // the parity hook: alpha/beta/delta/r/s terms zeroed, C and H apart, nothing assembled
+  SplitPart,  // a split proof's shard: the full augmentation (on shard 0's bases), no assembly; the
+              // part A' | B1' | B2' | C' + H | infinity goes to pinned + 512
+};
+
+enum class Schedule { Lowlat, Front, Chain };  // run_lowlat, run_front, run_chain
+
+// How one proof runs on its slot: decided once (plan_proof), then only read.
+struct ProofPlan {
+  ProofMode mode;
+  Schedule schedule;
+  bool share_b_sort;  // B2 accumulates from B1's sorted pairs (b2_from_b1_sort)
+  bool light_first;   // run_chain: ABC / NTT ahead of the witness-scalar MSMs (the stagger)
+  bool joint_tails;   // the G2 tail joins the G1 tails' launches (msm_tails_joint)
+  bool fast_wsum;     // the shorter-chain bucket reduction (msm.h MSM_WSUM_Q_FAST)
+  bool graph;         // replayed from the slot's graph (enqueue_proof_graph), witness staged
+};
+
+// The plan of the next proof of key k on slot s; batch_of_one: it is its batch's only proof.
+ProofPlan plan_proof(const SchedOpts& o, const zkfl_key* k, const ProofSlot* s, ProofMode mode, bool batch_of_one,
+                     const Profiler* prof) {
+  ProofPlan p = {};
+  p.mode = mode;
+  // the latency schedule and graph replay serve whole proofs of the plain build on a key whose B
+  // queries share a sort; a serialized profile wants one stream, launch by launch
+  const bool plain = mode == ProofMode::Proof && k->share_b && !prof->serialize && !ZK_KNOCKOUT;
+  // a batch of one proof runs the latency schedule (ZKFL_LOWLAT=0: a one-stream schedule)
+  const bool want_lowlat = batch_of_one && o.lowlat;
+  // graph replay from a slot's second proof on (a one-off proof pays no capture); the latency
+  // schedule is never captured
+  p.graph = o.graph && s->w_stage && !want_lowlat && plain && !prof->on && s->direct_proofs > 0;
+  // B1's digit sort also serves B2 (same scalars, same index map).  A key whose two index maps differ
+  // runs B2 as an MSM of its own (own sort, own tail).
+  p.share_b_sort = k->share_b && !(ZK_KNOCKOUT & 32);
+  if (want_lowlat && plain) {
+    p.schedule = Schedule::Lowlat;
+    p.fast_wsum = o.fast_wsum;  // (ZKFL_FAST_WSUM=0 keeps the throughput reduction: A/B)
+    return p;
+  }
+  // Small keys: the G2 tail joins the G1 tails' launches (msm_tails_joint) instead of running right
+  // after B2 -- config 5 2,712 vs 2,385 proofs/s (3 same-box alternations); the metric key keeps the
+  // separate tails (M 433 vs 439 and 431 vs 433 with them joint, two boxes:
+  // profiles/r06_ab_joint_tails.log, r06_ab_front.log)
+  p.joint_tails = p.share_b_sort && k->front;
+  // and their three G1 MSMs sort and accumulate together (run_front).  The parity hook keeps the
+  // chain, which returns C and H apart; a split proof's shard never has k->front (nshards == 1).
+  const bool front = p.joint_tails && mode != ProofMode::Parts && !(ZK_KNOCKOUT & 2);
+  p.schedule = front ? Schedule::Front : Schedule::Chain;
+  // Stage order of the chain.  Every slot runs the same chain, so under load the slots move as a
+  // convoy: the accumulations fill the GPU one at a time, and the slots that leave them together
+  // reach ABC + NTT together -- the wave timeline (tools/wtrace.py) showed stretches of ~4 ms with
+  // no accumulation resident at all.  Staggered (the default; ZKFL_STAGGER=0 turns it off): odd
+  // slots run ABC + NTT before their witness-scalar MSMs instead of after, so their light phase falls
+  // beside the others' heavy one (+2.3 %, 407.5 vs 398.6 proofs/s, 3 same-box alternations, DESIGN §5).
+  p.light_first = !front && o.stagger && (s->index & 1) && !prof->serialize;
+  // Small keys (domain <= 2^ZKFL_SMALL_LOGN, default 2^16: config 5's circuits) take the
+  // shorter-chain reduction in batches too: their proofs are chains of small latency-bound kernels
+  // that leave most of the GPU idle (config-5 wave trace: SIMD share 0.135 with a wave resident 99%
+  // of the time), so the reduction's extra waves are free and its shorter chain is not.
+  p.fast_wsum = o.fast_wsum && k->logn <= o.small_logn;
+  return p;
+}
+
+inline const GlvScalar* glv_halves(const ProofSlot* s) {  // s1, s2, r1, r2 behind r, s in d_rs
+  return reinterpret_cast<const GlvScalar*>(reinterpret_cast<const uint8_t*>(s->d_rs) + 64);
+}
+
+// Step: k_proof_start on the slot's stream, after the host has put r, s and the GLV halves into
+// the pinned buffer -- r, s and the halves to the device, the blinding scalars behind h, the tails
+// this plan accumulates into emptied: G1 A, B1, C + H, [H]; G2 B2 when it shares B1's sort (its own
+// msm_run empties its tail itself).  A graph-replayed proof stages its witness here.
+void start(zkfl_key* k, ProofSlot* s, const ProofPlan& p) {
+  // C + H is one MSM into tail 2 (res[2] = C' + H, res[3] = infinity); the parity hook's are apart
+  const bool parts = p.mode == ProofMode::Parts;
+  const int ntails = parts ? 4 : 3;
+  ProofStart ps = {};
+  auto add = [&](void* buckets, size_t bytes, uint32_t* nnz, uint32_t* live) {
+    ps.buckets[ps.n] = static_cast<uint4*>(buckets);
+    ps.nvec[ps.n] = (uint32_t)(bytes / sizeof(uint4));
+    ps.nnz[ps.n] = nnz;
+    ps.live[ps.n] = live;
+    ps.n++;
+  };
+  const size_t nb = msm_nb_of(k->msm_c);
+  for (int i = 0; i < ntails; i++) add(s->g1t[i].buckets, nb * sizeof(G1P), s->g1t[i].nnz, s->g1t[i].live);
+  if (p.share_b_sort) add(s->g2t.buckets, nb * sizeof(G2P), s->g2t.nnz, s->g2t.live);
+  uint32_t* res3 = parts ? nullptr : reinterpret_cast<uint32_t*>(s->res + 3);
+  if (p.graph) {  // from the address enqueue_proof left in the pinned buffer
+    ps.w_src_host = reinterpret_cast<const uint64_t*>(s->pinned + W_PTR_OFF);
+    ps.w_dst = reinterpret_cast<uint4*>(s->w_stage);
+    ps.w_nvec = (uint32_t)((size_t)k->nVars * 32 / sizeof(uint4));
+  }
+  proof_start(s->st_main, reinterpret_cast<const uint32_t*>(s->pinned + 256), reinterpret_cast<uint32_t*>(s->d_rs),
+              s->extra, parts, res3, ps);
+}
+
+// Step: ABC (a, b, c on the domain), the coset NTT of all three and h = a b - c (std form: the H
+// MSM's scalars) on stream st.
+hipError_t abc_ntt(zkfl_key* k, ProofSlot* s, const Fr* d_w, hipStream_t st, Profiler* prof) {
   const size_t n = k->n;
   int pi = prof->begin("abc", st);
   if (k->K) {
@@ -270,101 +367,84 @@ int enqueue_abc_ntt(zkfl_key* k, ProofSlot* s, const Fr* d_w, hipStream_t st, Pr
   abc_rows(st, k->rows, n, (uint32_t)k->K, s->abc_head, s->abc_tail, s->abc);
   prof->end(pi, st, (double)k->K);
   pi = prof->begin("ntt", st);
-  if (!(ZK_KNOCKOUT & 4)) HIP_TRY(ntt_coset_shift(k->ntt, s->abc, 3, n, st), "ntt");
+  if (!(ZK_KNOCKOUT & 4)) ZK_CHECK(ntt_coset_shift(k->ntt, s->abc, 3, n, st));
   prof->end(pi, st, 3.0 * (double)n);
   join_h(st, s->abc, n, s->h);
+  return hipSuccess;
+}
+
+// Step: B2 from B1's sort.  `sorted` holds the pairs of B's digit sort (whoever sorted, on
+// whichever stream, ordered before st here); B2 accumulates from them on st before anything reuses
+// that scratch.  Its tail counts with B1's nnz, copied unless the two alias (ProofSlot::nnz_alias).
+hipError_t b2_from_b1_sort(zkfl_key* k, ProofSlot* s, const MsmScratch<FqOps>& sorted, hipStream_t st,
+                           Profiler* prof) {
+  if (!s->nnz_alias)
+    ZK_CHECK(hipMemcpyAsync(s->g2t.nnz, s->g1t[1].nnz, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  return msm_accumulate_sorted(k->bB2, sorted.keys_out, sorted.vals_out, s->g2t, st, prof, "msm_accumulate_g2");
+}
+
+// Step: what leaves a one-stream schedule -- a split proof's part and its download, a proof's
+// assembly (pi_a, pi_b, pi_c) into the pinned buffer, nothing for the parity hook (its caller
+// reads res, resB2 and h).
+int finish(ProofSlot* s, const ProofPlan& p, Profiler* prof) {
+  hipStream_t st = s->st_main;
+  if (p.mode == ProofMode::SplitPart) {
+    part_out(st, s->res, s->resB2, s->d_parts);
+    HIP_TRY(hipMemcpyAsync(s->pinned + 512, s->d_parts, PART_WORDS * 4, hipMemcpyDeviceToHost, st), "download part");
+  }
+  if (p.mode == ProofMode::Proof && !(ZK_KNOCKOUT & 1)) {
+    const int pa = prof->begin("assemble", st);
+    assemble(st, 1, s->res, s->resB2, glv_halves(s), proof_out(s));
+    prof->end(pa, st, 1.0);
+  }
   return ZKFL_OK;
-}
-
-// The latency schedules reduce their buckets with the shorter-chain reduction (msm.h
-// MSM_WSUM_Q_FAST); ZKFL_FAST_WSUM=0 keeps the throughput form (A/B).
-bool lowlat_fast_wsum() {
-  static const bool on = !getenv("ZKFL_FAST_WSUM") || atoi(getenv("ZKFL_FAST_WSUM")) != 0;
-  return on;
-}
-
-// Small keys (domain <= 2^ZKFL_FAST_WSUM_LOGN, default 2^16: config 5's circuits) take the
-// shorter-chain reduction in batches too: their proofs are chains of small latency-bound kernels
-// that leave most of the GPU idle (config-5 wave trace: SIMD share 0.135 with a wave resident 99%
-// of the time), so the reduction's extra waves are free and its shorter chain is not.
-bool small_key_fast_wsum(const zkfl_key* k) {
-  static const int logn = getenv("ZKFL_FAST_WSUM_LOGN") ? atoi(getenv("ZKFL_FAST_WSUM_LOGN")) : 16;
-  return lowlat_fast_wsum() && k->logn <= logn;
 }
 
 // One proof alone (a batch of one: the CLI's `groth16 prove`, the API's prove): its latency is
 // the metric, and the GPU is mostly idle along the one-stream chain, so the two long chains start
 // at once on streams of their own:
-//   main : r, s, tails reset [ev ready] ABC, coset NTT, join, C + H (sort + accumulate), its tail,
-//          wait(B2, T), k_assemble_c, proof D2H [ev_done]
+//   main : [start] [ev ready] ABC, coset NTT, join, C + H (sort + accumulate), its tail,
+//          wait(B2, T), k_assemble_c (pi_c, pi_b) into the pinned buffer
 //   lat0 : wait(ev ready) B sort (own scratch) [ev B sorted] B2 + its tail [ev B2]
 //   lat1 : wait(ev B sorted) B1, A (sort into its own scratch + accumulate), the tails of A and
 //          B1, k_assemble_t (T = s pi_A + r B1, pi_a) [ev T]
-// Same proof bytes as the one-stream schedule (k_assemble_t / _c form the same points).  The
+// Same proof bytes as the one-stream schedules (k_assemble_t / _c form the same points).  The
 // round-4 schedule ran A and B1 on the main stream ahead of ABC / NTT (4.10 vs 4.16 ms then); with
 // the row assembly and the divsteps inversions the overlap wins: 3.586 vs 3.712 ms, 3 same-box
 // alternations (profiles/r06_ab_lowlat2.log), and the round-4 one was deleted, with its
 // per-segment graph replay (ZKFL_GRAPH=2: no gain, profiles/r04_ab_lowlat_seg_graphs.log).
-
-// ZKFL_GRAPH (default 1): graph replay of the one-stream proof chain (0: launch kernel by kernel)
-int graph_mode() {
-  static const int m = getenv("ZKFL_GRAPH") ? atoi(getenv("ZKFL_GRAPH")) : 1;
-  return m;
-}
-
-// (the schedule above)
-int enqueue_proof_lowlat(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w) {
-  Profiler* prof = &ctx->prof;
-  hipStream_t st = s->st_main;
-  for (int i = 0; i < 2; i++)
-    if (!s->st_lat[i]) HIP_TRY(hipStreamCreateWithFlags(&s->st_lat[i], hipStreamNonBlocking), "stream");
-  for (int i = 0; i < 3; i++)
-    if (!s->ev_lat[i]) HIP_TRY(hipEventCreateWithFlags(&s->ev_lat[i], hipEventDisableTiming), "event");
-  if (!s->g1s_b.keys_out) HIP_TRY(msm_scratch_alloc(s->g1s_b, k->bB1.n, k->msm_c, st), "B sort scratch");
-  if (!s->g1s_a.keys_out) HIP_TRY(msm_scratch_alloc(s->g1s_a, k->bA.n, k->msm_c, st), "A sort scratch");
-  hipStream_t sb = s->st_lat[0], sa = s->st_lat[1];
+int run_lowlat(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Profiler* prof) {
+  HIP_TRY(slot_side_resources(s, k, true), "latency schedule resources");
+  hipStream_t st = s->st_main, sb = s->st_lat[0], sa = s->st_lat[1];
   // ev_lat[0] marks "ready" then (re-recorded on lat0) "B sorted": each wait is enqueued before
   // the next record, so every wait sees the record it was meant for
   hipEvent_t ev = s->ev_lat[0], ev_b2 = s->ev_lat[1], ev_t = s->ev_lat[2];
-  const uint32_t* W = (const uint32_t*)d_w;
-  const uint32_t* E = (const uint32_t*)s->extra;
+  const uint32_t *W = (const uint32_t*)d_w, *E = (const uint32_t*)s->extra;
   MsmTail<FqOps>* tails[3] = {&s->g1t[0], &s->g1t[1], &s->g1t[2]};
+  G1P* outs[3] = {s->res + 0, s->res + 1, s->res + 2};
   MsmTail<Fq2Ops>* t2 = &s->g2t;
   G2P* o2 = s->resB2;
   HIP_TRY(hipEventRecord(ev, st), "event");  // (tails emptied by k_proof_start)
   // lat0: B's sort, then B2 and its tail
   HIP_TRY(hipStreamWaitEvent(sb, ev, 0), "wait");
   HIP_TRY(msm_sort(k->bB1, s->g1s_b, s->g1t[1].nnz, W, E, sb), "msm B sort");
-  if (!s->nnz_alias)
-    HIP_TRY(hipMemcpyAsync(s->g2t.nnz, s->g1t[1].nnz, sizeof(uint32_t), hipMemcpyDeviceToDevice, sb), "nnz");
   HIP_TRY(hipEventRecord(ev, sb), "event");
   HIP_TRY(hipStreamWaitEvent(sa, ev, 0), "wait");
-  HIP_TRY(msm_accumulate_sorted(k->bB2, s->g1s_b.keys_out, s->g1s_b.vals_out, s->g2t, sb, prof,
-                                   "msm_accumulate_g2"), "msm B2");
-  HIP_TRY(msm_tails(&t2, &o2, 1, sb, lowlat_fast_wsum()), "msm B2 tail");
+  HIP_TRY(b2_from_b1_sort(k, s, s->g1s_b, sb, prof), "msm B2");
+  HIP_TRY(msm_tails(&t2, &o2, 1, sb, p.fast_wsum), "msm B2 tail");
   HIP_TRY(hipEventRecord(ev_b2, sb), "event");
   // lat1: B1 (B's pairs), A, their tails, then T = s pi_A + r B1 and pi_a
   HIP_TRY(msm_accumulate_sorted(k->bB1, s->g1s_b.keys_out, s->g1s_b.vals_out, s->g1t[1], sa, prof,
                                    "msm_accumulate_g1"), "msm B1");
   HIP_TRY(msm_accumulate(k->bA, s->g1s_a, s->g1t[0], W, E, sa, prof, "msm_accumulate_g1"), "msm A");
-  {
-    G1P* outs[2] = {s->res + 0, s->res + 1};
-    HIP_TRY(msm_tails(tails, outs, 2, sa, lowlat_fast_wsum()), "msm tails A, B1");
-  }
-  assemble_t(sa, s->res, reinterpret_cast<const GlvScalar*>(reinterpret_cast<const uint8_t*>(s->d_rs) + 64),
-             proof_out(s));
+  HIP_TRY(msm_tails(tails, outs, 2, sa, p.fast_wsum), "msm tails A, B1");
+  assemble_t(sa, s->res, glv_halves(s), proof_out(s));
   HIP_TRY(hipEventRecord(ev_t, sa), "event");
   // main: ABC / NTT / h, C + H and its tail, then pi_c and pi_b
-  {
-    const int rc = enqueue_abc_ntt(k, s, d_w, st, prof);
-    if (rc) return rc;
-  }
+  HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
   HIP_TRY(msm_accumulate(k->bCH, s->g1s, s->g1t[2], W, (const uint32_t*)s->h, st, prof, "msm_accumulate_g1"),
           "msm C+H");
-  {
-    G1P* out2 = s->res + 2;
-    HIP_TRY(msm_tails(&tails[2], &out2, 1, st, lowlat_fast_wsum()), "msm tail C+H");
-  }
+  HIP_TRY(msm_tails(&tails[2], &outs[2], 1, st, p.fast_wsum), "msm tail C+H");
   HIP_TRY(hipStreamWaitEvent(st, ev_b2, 0), "wait");
   HIP_TRY(hipStreamWaitEvent(st, ev_t, 0), "wait");
   const int pa = prof->begin("assemble", st);
@@ -373,218 +453,138 @@ int enqueue_proof_lowlat(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w
   return ZKFL_OK;
 }
 
-// The device work of one proof on the slot's stream (the latency schedule adds two of its own),
-// after the host has put r, s and the GLV halves into the pinned buffer.
-int enqueue_proof_body(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, int plain, int lowlat) {
-  Profiler* prof = &ctx->prof;
+// Small keys, one stream:
+//   [start] ABC, coset NTT, join, A, B1 and C + H sorted together (each in its own scratch) and
+//   accumulated in one launch, B2 from B1's pairs, the G1 and G2 tails as one batch, [finish]
+// Their proofs are chains of latency-bound launches: fewer links, shorter chain (config 5 2,802 vs
+// 2,748 proofs/s, 3 same-box alternations, profiles/r06_ab_front.log).
+int run_front(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Profiler* prof) {
   hipStream_t st = s->st_main;
-  int pp = prof->begin("prove", st);
-  const bool lowlat_path = lowlat && plain == 0 && k->share_b && !prof->serialize && !ZK_KNOCKOUT;
-  // C + H as one MSM into tail 2 (res[2] = C' + H, res[3] = infinity); the parity hook (plain = 1)
-  // returns them apart: C = the C + H MSM over (witness, zero h), H = over (zero witness, h)
-  const bool merge = plain != 1;
-  const bool split_ch = !merge;
-  const int ntails = merge ? 3 : 4;
-  // B1's digit sort also serves B2 (same scalars, same index map), so B2 runs right after B1,
-  // before C + H reuses the sort scratch.  A key whose two index maps differ runs B2 as an MSM of its
-  // own (own sort, own tail).
-  const bool share = k->share_b && !(ZK_KNOCKOUT & 32);
-  {
-    // the tails this chain accumulates into: G1 A, B1, C + H, [H]; G2 B2 when it shares B1's sort
-    // (its own msm_run empties its tail itself)
-    ProofStart ps = {};
-    auto add = [&](void* buckets, size_t bytes, uint32_t* nnz, uint32_t* live) {
-      ps.buckets[ps.n] = static_cast<uint4*>(buckets);
-      ps.nvec[ps.n] = (uint32_t)(bytes / sizeof(uint4));
-      ps.nnz[ps.n] = nnz;
-      ps.live[ps.n] = live;
-      ps.n++;
-    };
-    const size_t nb = msm_nb_of(k->msm_c);
-    for (int i = 0; i < ntails; i++) add(s->g1t[i].buckets, nb * sizeof(G1P), s->g1t[i].nnz, s->g1t[i].live);
-    if (share) add(s->g2t.buckets, nb * sizeof(G2P), s->g2t.nnz, s->g2t.live);
-    uint32_t* res3 = merge ? reinterpret_cast<uint32_t*>(s->res + 3) : nullptr;
-    if (s->w_stage && d_w == s->w_stage) {  // graph replay (enqueue_proof): stage the witness here
-      ps.w_src_host = reinterpret_cast<const uint64_t*>(s->pinned + W_PTR_OFF);
-      ps.w_dst = reinterpret_cast<uint4*>(s->w_stage);
-      ps.w_nvec = (uint32_t)((size_t)k->nVars * 32 / sizeof(uint4));
-    }
-    proof_start(st, reinterpret_cast<const uint32_t*>(s->pinned + 256), reinterpret_cast<uint32_t*>(s->d_rs), s->extra,
-                plain == 1, res3, ps);
-  }
-  if (lowlat_path) {
-    const int rc = enqueue_proof_lowlat(ctx, k, s, d_w);
-    if (rc) return rc;
-    prof->end(pp, st, 1.0);
-    return ZKFL_OK;
-  }
-  const uint32_t* W = (const uint32_t*)d_w;
-  const uint32_t* E = (const uint32_t*)s->extra;
-  MsmTail<FqOps>* tails[4] = {&s->g1t[0], &s->g1t[1], &s->g1t[2], &s->g1t[3]};
-  if (split_ch && !k->dbg_zero) return fail(ZKFL_E_ARG, "parity hook: zeros not allocated");
-  const uint32_t* Z = (const uint32_t*)k->dbg_zero;
-  // Stage order.  Every slot runs the same chain, so under load the slots move as a convoy: the
-  // accumulations fill the GPU one at a time, and the slots that leave them together reach ABC +
-  // NTT together -- the wave timeline (tools/wtrace.py) showed stretches of ~4 ms with no
-  // accumulation resident at all.  Staggered (the default; ZKFL_STAGGER=0 turns it off): odd slots
-  // run ABC + NTT before their witness-scalar MSMs instead of after, so their light phase falls
-  // beside the others' heavy one (+2.3 %, 407.5 vs 398.6 proofs/s, 3 same-box alternations, DESIGN §5).
-  static const int stagger = getenv("ZKFL_STAGGER") ? atoi(getenv("ZKFL_STAGGER")) : 1;
-  const bool light_first = stagger && (s->index & 1) && !prof->serialize;
-  // Small keys: the G2 tail joins the G1 tails' launches (msm_tails_joint) instead of running right
-  // after B2 -- config 5 2,712 vs 2,385 proofs/s (3 same-box alternations); the metric key keeps the
-  // separate tails (M 433 vs 439 and 431 vs 433 with them joint, two boxes:
-  // profiles/r06_ab_joint_tails.log, r06_ab_front.log)
-  const bool joint = share && k->front;
-  if (!share && !(ZK_KNOCKOUT & 32))
-    HIP_TRY(msm_run(k->bB2, s->g2s, s->g2t, W, E, s->resB2, st, prof, "msm_accumulate_g2"), "msm B2");
-  auto abc_ntt = [&]() { return enqueue_abc_ntt(k, s, d_w, st, prof); };
-  // main: the witness-scalar G1 MSMs, then ABC / NTT / H, then all four G1 tails in one batch
+  const uint32_t *W = (const uint32_t*)d_w, *E = (const uint32_t*)s->extra;
+  HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
+  const MsmBases<FqOps>* bs[3] = {&k->bA, &k->bB1, &k->bCH};
+  MsmScratch<FqOps>* ss[3] = {&s->g1s_a, &s->g1s_b, &s->g1s};
+  MsmTail<FqOps>* tails[3] = {&s->g1t[0], &s->g1t[1], &s->g1t[2]};
+  uint32_t* nn[3] = {s->g1t[0].nnz, s->g1t[1].nnz, s->g1t[2].nnz};
+  const uint32_t* sc[3] = {W, W, W};
+  const uint32_t* ex[3] = {E, E, (const uint32_t*)s->h};
+  HIP_TRY(msm_sort_multi(bs, ss, nn, sc, ex, 3, st), "msm A, B1, C+H sorts");
+  const uint16_t* kk[3] = {ss[0]->keys_out, ss[1]->keys_out, ss[2]->keys_out};
+  const uint32_t* vv[3] = {ss[0]->vals_out, ss[1]->vals_out, ss[2]->vals_out};
+  HIP_TRY(msm_accumulate_sorted_multi(bs, kk, vv, tails, 3, st), "msm A, B1, C+H");
+  HIP_TRY(b2_from_b1_sort(k, s, s->g1s_b, st, prof), "msm B2");
+  G1P* outs[3] = {s->res + 0, s->res + 1, s->res + 2};
+  MsmTail<Fq2Ops>* t2 = &s->g2t;
+  G2P* o2 = s->resB2;
+  HIP_TRY(msm_tails_joint(tails, outs, 3, &t2, &o2, 1, st, p.fast_wsum), "msm tails (G1 + G2)");
+  return finish(s, p, prof);
+}
+
+// Every other proof, a serial chain on the slot's one stream:
+//   [start] [B2 as an MSM of its own: a key whose B queries do not share a sort]
+//   [ABC, coset NTT, join: light_first] A, B sort, B1, B2 from B1's pairs [B2's tail unless joint]
+//   [ABC, coset NTT, join: otherwise] C + H, the G1 tails as one batch [with B2's: joint], [finish]
+// The parity hook runs the C + H MSM twice over the key's zero vectors and finishes four tails:
+// C = over (witness, zero h) in C + H's place before ABC / NTT, H = over (zero witness, h) after.
+int run_chain(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Profiler* prof) {
+  hipStream_t st = s->st_main;
+  const bool parts = p.mode == ProofMode::Parts;
+  if (parts && !k->dbg_zero) return fail(ZKFL_E_ARG, "parity hook: zeros not allocated");
+  const uint32_t *W = (const uint32_t*)d_w, *E = (const uint32_t*)s->extra, *H = (const uint32_t*)s->h,
+                 *Z = (const uint32_t*)k->dbg_zero;
 #if ZK_KNOCKOUT & 2
   MsmScratch<FqOps>&sA = s->g1s_ko[0], &sB = s->g1s_ko[1], &sCH = s->g1s_ko[2];
 #else
   MsmScratch<FqOps>&sA = s->g1s, &sB = s->g1s, &sCH = s->g1s;
 #endif
-  // small keys: ABC / NTT, then A, B1 and C + H sorted together and accumulated in one launch, B2
-  // from B1's pairs (their proofs are chains of latency-bound launches: fewer links, shorter chain;
-  // config 5 2,802 vs 2,748 proofs/s, 3 same-box alternations, profiles/r06_ab_front.log)
-  const bool front = joint && merge && !(ZK_KNOCKOUT & 2) && s->g1s_a.keys_out && s->g1s_b.keys_out;
-  if (front) {
-    const int rc = abc_ntt();
-    if (rc) return rc;
-    const MsmBases<FqOps>* bs[3] = {&k->bA, &k->bB1, &k->bCH};
-    MsmScratch<FqOps>* ss[3] = {&s->g1s_a, &s->g1s_b, &s->g1s};
-    uint32_t* nn[3] = {s->g1t[0].nnz, s->g1t[1].nnz, s->g1t[2].nnz};
-    const uint32_t* sc[3] = {W, W, W};
-    const uint32_t* ex[3] = {E, E, (const uint32_t*)s->h};
-    HIP_TRY(msm_sort_multi(bs, ss, nn, sc, ex, 3, st), "msm A, B1, C+H sorts");
-    const uint16_t* kk[3] = {ss[0]->keys_out, ss[1]->keys_out, ss[2]->keys_out};
-    const uint32_t* vv[3] = {ss[0]->vals_out, ss[1]->vals_out, ss[2]->vals_out};
-    HIP_TRY(msm_accumulate_sorted_multi(bs, kk, vv, tails, 3, st), "msm A, B1, C+H");
-    if (!s->nnz_alias)
-      HIP_TRY(hipMemcpyAsync(s->g2t.nnz, s->g1t[1].nnz, sizeof(uint32_t), hipMemcpyDeviceToDevice, st), "nnz");
-    HIP_TRY(msm_accumulate_sorted(k->bB2, ss[1]->keys_out, ss[1]->vals_out, s->g2t, st, prof, "msm_accumulate_g2"),
-            "msm B2");
-  }
-  if (light_first && !front) {
-    const int rc = abc_ntt();
-    if (rc) return rc;
-  }
-  if (!front) HIP_TRY(msm_accumulate(k->bA, sA, s->g1t[0], W, E, st, prof, "msm_accumulate_g1"), "msm A");
-  if (front) {
-  } else if (share) {
-    MsmTail<Fq2Ops>* t2 = &s->g2t;
-    G2P* o2 = s->resB2;
+  MsmTail<FqOps>* tails[4] = {&s->g1t[0], &s->g1t[1], &s->g1t[2], &s->g1t[3]};
+  G1P* outs[4] = {s->res + 0, s->res + 1, s->res + 2, s->res + 3};
+  MsmTail<Fq2Ops>* t2 = &s->g2t;
+  G2P* o2 = s->resB2;
+  if (!p.share_b_sort && !(ZK_KNOCKOUT & 32))
+    HIP_TRY(msm_run(k->bB2, s->g2s, s->g2t, W, E, s->resB2, st, prof, "msm_accumulate_g2"), "msm B2");
+  if (p.light_first) HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
+  HIP_TRY(msm_accumulate(k->bA, sA, s->g1t[0], W, E, st, prof, "msm_accumulate_g1"), "msm A");
+  if (p.share_b_sort) {  // B2 right after B1, before C + H reuses the sort scratch
     HIP_TRY(msm_sort(k->bB1, sB, s->g1t[1].nnz, W, E, st), "msm B1 sort");
-    HIP_TRY(msm_accumulate_sorted(k->bB1, sB.keys_out, sB.vals_out, s->g1t[1], st, prof,
-                                     "msm_accumulate_g1"), "msm B1");
-    if (!s->nnz_alias)
-      HIP_TRY(hipMemcpyAsync(s->g2t.nnz, s->g1t[1].nnz, sizeof(uint32_t), hipMemcpyDeviceToDevice, st), "nnz");
-    HIP_TRY(msm_accumulate_sorted(k->bB2, sB.keys_out, sB.vals_out, s->g2t, st, prof,
-                                     "msm_accumulate_g2"), "msm B2");
-    if (!joint) HIP_TRY(msm_tails(&t2, &o2, 1, st, small_key_fast_wsum(k)), "msm B2 tail");
+    HIP_TRY(msm_accumulate_sorted(k->bB1, sB.keys_out, sB.vals_out, s->g1t[1], st, prof, "msm_accumulate_g1"),
+            "msm B1");
+    HIP_TRY(b2_from_b1_sort(k, s, sB, st, prof), "msm B2");
+    if (!p.joint_tails) HIP_TRY(msm_tails(&t2, &o2, 1, st, p.fast_wsum), "msm B2 tail");
   } else {
     HIP_TRY(msm_accumulate(k->bB1, sB, s->g1t[1], W, E, st, prof, "msm_accumulate_g1"), "msm B1");
   }
-  if (split_ch)
-    HIP_TRY(msm_accumulate(k->bCH, s->g1s, s->g1t[2], W, Z, st, prof, "msm_accumulate_g1"), "msm C");
-  if (!light_first && !front) {
-    const int rc = abc_ntt();
-    if (rc) return rc;
-  }
-  if (front) {
-  } else if (merge) {
-    HIP_TRY(msm_accumulate(k->bCH, sCH, s->g1t[2], W, (const uint32_t*)s->h, st, prof, "msm_accumulate_g1"),
-            "msm C+H");
-  } else {
-    HIP_TRY(msm_accumulate(k->bCH, s->g1s, s->g1t[3], Z, (const uint32_t*)s->h, st, prof, "msm_accumulate_g1"),
-            "msm H");
-  }
-  {
-    G1P* outs[4] = {s->res + 0, s->res + 1, s->res + 2, s->res + 3};
-    if (joint) {
-      MsmTail<Fq2Ops>* t2 = &s->g2t;
-      G2P* o2 = s->resB2;
-      HIP_TRY(msm_tails_joint(tails, outs, ntails, &t2, &o2, 1, st, small_key_fast_wsum(k)), "msm tails (G1 + G2)");
-    } else {
-      HIP_TRY(msm_tails(tails, outs, ntails, st, small_key_fast_wsum(k)), "msm tails");
-    }
-  }
-  if (plain == 2) {
-    part_out(st, s->res, s->resB2, s->d_parts);
-    HIP_TRY(hipMemcpyAsync(s->pinned + 512, s->d_parts, PART_WORDS * 4, hipMemcpyDeviceToHost, st), "download part");
-  }
-  if (!plain && !(ZK_KNOCKOUT & 1)) {
-    const int pa = prof->begin("assemble", st);
-    assemble(st, 1, s->res, s->resB2, reinterpret_cast<const GlvScalar*>(reinterpret_cast<const uint8_t*>(s->d_rs) + 64),
-             proof_out(s));
-    prof->end(pa, st, 1.0);
-  }
-  prof->end(pp, st, 1.0);
-  return ZKFL_OK;
+  if (parts) HIP_TRY(msm_accumulate(k->bCH, s->g1s, s->g1t[2], W, Z, st, prof, "msm_accumulate_g1"), "msm C");
+  if (!p.light_first) HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
+  if (parts)
+    HIP_TRY(msm_accumulate(k->bCH, s->g1s, s->g1t[3], Z, H, st, prof, "msm_accumulate_g1"), "msm H");
+  else
+    HIP_TRY(msm_accumulate(k->bCH, sCH, s->g1t[2], W, H, st, prof, "msm_accumulate_g1"), "msm C+H");
+  const int ntails = parts ? 4 : 3;
+  if (p.joint_tails)
+    HIP_TRY(msm_tails_joint(tails, outs, ntails, &t2, &o2, 1, st, p.fast_wsum), "msm tails (G1 + G2)");
+  else
+    HIP_TRY(msm_tails(tails, outs, ntails, st, p.fast_wsum), "msm tails");
+  return finish(s, p, prof);
 }
 
-// Graph replay of the one-stream chain (the default; ZKFL_GRAPH=0 launches kernel by kernel;
-// config 5 +3.5%, 1894 vs 1831 proofs/s, M +0.6% inside the spread, 3 same-box alternations,
-// profiles/r04_ab_c5_small_keys.log, r04_ab_m_graph_target.log): a slot captures its proof's ~40 launches
-// once per witness address (enqueue_proof passes the slot's witness stage, so once per slot) and
-// then launches the graph -- one host call per proof instead of one per kernel.  Kernel arguments
-// are the slot's own buffers, the key's and the witness address, all fixed per cache entry; r and s
-// reach the device through the captured copy from the slot's pinned buffer.
-int enqueue_proof_graph(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, int plain) {
-  hipStream_t st = s->st_main;
-  ProofSlot::Graph* gr = nullptr;
-  for (auto& x : s->graphs)
-    if (x.w == d_w) gr = &x;
-  if (!gr) {
-    if (s->graphs.size() >= 8) {  // bounded cache: drop the oldest
-      ProofSlot::Graph& o = s->graphs.front();
-      if (o.ex) (void)hipGraphExecDestroy(o.ex);
-      if (o.g) (void)hipGraphDestroy(o.g);
-      s->graphs.erase(s->graphs.begin());
-    }
-    ProofSlot::Graph ng;
-    ng.w = d_w;
-    HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal), "begin capture");
-    const int rc = enqueue_proof_body(ctx, k, s, d_w, plain, 0);
-    const hipError_t ec = hipStreamEndCapture(st, &ng.g);
-    if (rc) {
-      if (ng.g) (void)hipGraphDestroy(ng.g);
-      return rc;
-    }
-    HIP_TRY(ec, "end capture");
-    const hipError_t ei = hipGraphInstantiate(&ng.ex, ng.g, nullptr, nullptr, 0);
-    if (ei != hipSuccess) {
-      (void)hipGraphDestroy(ng.g);
-      return hip_fail(ei, "graph instantiate");
-    }
-    s->graphs.push_back(ng);
-    gr = &s->graphs.back();
-  }
-  HIP_TRY(hipGraphLaunch(gr->ex, st), "graph launch");
-  return ZKFL_OK;
-}
-
-int enqueue_proof(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, const uint32_t rs_host[16], int plain,
-                  int lowlat = 0) {
+// The device work of one proof, launch by launch: start, then its plan's schedule.
+int run_proof(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p) {
   Profiler* prof = &ctx->prof;
+  const int pp = prof->begin("prove", s->st_main);
+  start(k, s, p);
+  const int rc = p.schedule == Schedule::Lowlat  ? run_lowlat(k, s, d_w, p, prof)
+                 : p.schedule == Schedule::Front ? run_front(k, s, d_w, p, prof)
+                                                 : run_chain(k, s, d_w, p, prof);
+  if (rc) return rc;
+  prof->end(pp, s->st_main, 1.0);
+  return ZKFL_OK;
+}
+
+// Graph replay of the one-stream schedules (the default; ZKFL_GRAPH=0 launches kernel by kernel;
+// config 5 +3.5%, 1894 vs 1831 proofs/s, M +0.6% inside the spread, 3 same-box alternations,
+// profiles/r04_ab_c5_small_keys.log, r04_ab_m_graph_target.log): a slot captures its proof's ~40
+// launches once, over its witness stage, and then launches the graph -- one host call per proof
+// instead of one per kernel.  Kernel arguments are the slot's own buffers and the key's, all fixed,
+// as is the slot's plan; r and s reach the device through the captured copy from the slot's pinned
+// buffer.
+int enqueue_proof_graph(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const ProofPlan& p) {
+  hipStream_t st = s->st_main;
+  if (!s->graph_exec) {
+    HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal), "begin capture");
+    const int rc = run_proof(ctx, k, s, s->w_stage, p);
+    hipError_t e = hipStreamEndCapture(st, &s->graph);
+    if (rc == ZKFL_OK && e == hipSuccess) e = hipGraphInstantiate(&s->graph_exec, s->graph, nullptr, nullptr, 0);
+    if (rc || e != hipSuccess) {
+      if (s->graph) (void)hipGraphDestroy(s->graph);
+      s->graph = nullptr;
+      s->graph_exec = nullptr;
+      return rc ? rc : hip_fail(e, "graph capture");
+    }
+  }
+  HIP_TRY(hipGraphLaunch(s->graph_exec, st), "graph launch");
+  return ZKFL_OK;
+}
+
+// Enqueue one proof on a slot (asynchronous): r, s and their GLV halves into the pinned buffer,
+// the proof's plan, then the plan's graph or its launches [ev_done].
+int enqueue_proof(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, const uint32_t rs_host[16], ProofMode mode,
+                  bool batch_of_one) {
   memcpy(s->pinned + 256, rs_host, 64);
   GlvScalar* ks = reinterpret_cast<GlvScalar*>(s->pinned + 320);
   glv_split(rs_host + 8, ks[0], ks[1]);  // s -> s1, s2 (for pi_A, phi(pi_A))
   glv_split(rs_host, ks[2], ks[3]);      // r -> r1, r2 (for B1, phi(B1))
-  // graph replay from a slot's second proof on (a one-off proof pays no capture); the witness is
-  // staged into the slot's own buffer so the captured kernel arguments hold for every witness
-  const bool graph = graph_mode() && s->w_stage && !lowlat && plain == 0 && !prof->on && !prof->serialize &&
-                     k->share_b && !ZK_KNOCKOUT && s->direct_proofs > 0;
+  const ProofPlan p = plan_proof(ctx->opts, k, s, mode, batch_of_one, &ctx->prof);
   int rc;
-  if (graph) {
-    // k_proof_start copies the witness into the stage from the address left here
+  if (p.graph) {
+    // the witness is staged into the slot's own buffer so the captured kernel arguments hold for
+    // every witness: k_proof_start copies it into the stage from the address left here
     const uint64_t src = reinterpret_cast<uint64_t>(d_w);
     memcpy(s->pinned + W_PTR_OFF, &src, sizeof(src));
-    rc = enqueue_proof_graph(ctx, k, s, s->w_stage, plain);
+    rc = enqueue_proof_graph(ctx, k, s, p);
   } else {
     s->direct_proofs++;
-    rc = enqueue_proof_body(ctx, k, s, d_w, plain, lowlat);
+    rc = run_proof(ctx, k, s, d_w, p);
   }
   if (rc) return rc;
   HIP_TRY(hipEventRecord(s->ev_done, s->st_main), "event");
@@ -594,19 +594,19 @@ int enqueue_proof(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, const
 
 // Host wait for a device event.  hipEventSynchronize on these (non-blocking-sync) events spins a
 // host core for the whole wait: it was most of config 5's host CPU per proof (0.55-0.57 ms, 1.2
-// cores busy at ~2,100 proofs/s).  A batch (poll = true) polls instead, sleeping ZKFL_WAIT_US
-// (default 50) microseconds between queries: 0.13-0.16 ms per proof, 0.3 cores, throughput within
+// cores busy at ~2,100 proofs/s).  A batch (poll = true) polls instead, sleeping WAIT_US
+// microseconds between queries: 0.13-0.16 ms per proof, 0.3 cores, throughput within
 // the spread (2,091 vs 2,095 proofs/s, 3 same-box alternations, profiles/r05_ab_c5_fold_wait.log,
 // which A/Bs the waits beside a since-removed fold knob);
 // the scheduler refills a freed slot up to that much later, ~0.1% of an M step.  A proof alone (the
-// latency path) keeps the spin.  ZKFL_WAIT_US=0 spins everywhere.
+// latency path) keeps the spin.
+constexpr int WAIT_US = 50;
 static hipError_t host_wait(hipEvent_t ev, bool poll) {
-  static const int us = getenv("ZKFL_WAIT_US") ? atoi(getenv("ZKFL_WAIT_US")) : 50;
-  if (us <= 0 || !poll) return hipEventSynchronize(ev);
+  if (!poll) return hipEventSynchronize(ev);
   for (;;) {
     const hipError_t e = hipEventQuery(ev);
     if (e != hipErrorNotReady) return e;
-    std::this_thread::sleep_for(std::chrono::microseconds(us));
+    std::this_thread::sleep_for(std::chrono::microseconds(WAIT_US));
   }
 }
 
@@ -641,8 +641,6 @@ int run_jobs(zkfl_ctx* ctx, size_t n, GetJob job) {
     size_t issued = 0;  // proofs issued in this batch
   };
   std::vector<PerKey> cursor;
-  // a batch of one proof runs the low-latency schedule (ZKFL_LOWLAT=0: the one-stream chain)
-  static const int lowlat = getenv("ZKFL_LOWLAT") ? atoi(getenv("ZKFL_LOWLAT")) : 1;
   auto issue = [&](PerKey& pk, size_t i, const Job& J, const uint32_t* rsl) -> int {
     ProofSlot* s = nullptr;
     int rc = get_slot(J.key, pk.issued++, &s);
@@ -658,7 +656,7 @@ int run_jobs(zkfl_ctx* ctx, size_t n, GetJob job) {
       hipError_t e = hipStreamWaitEvent(s->st_main, J.w_ready, 0);
       if (e != hipSuccess) return hip_fail(e, "wait for the witness group");
     }
-    rc = enqueue_proof(ctx, J.key, s, J.w, rsl, J.part_out ? 2 : 0, n == 1 ? lowlat : 0);
+    rc = enqueue_proof(ctx, J.key, s, J.w, rsl, J.part_out ? ProofMode::SplitPart : ProofMode::Proof, n == 1);
     if (rc) return rc;
     s->busy = true;
     return ZKFL_OK;
@@ -869,11 +867,9 @@ int full_prove_piped(zkfl_ctx* ctx, size_t n, KeyOf key_of, ProgOf prog_of, GetI
       uint32_t nw = 0, nin = 0, np = 0;
       wprog_info(pk.prog, &nw, &nin, &np);
       pk.n_in = nin;
-      // one group >= the proofs a key holds in flight: the witness sets'
-      // reuse (enqueue_group) relies on it.  ZKFL_WIT_GROUP=m: m times that (a witness launch
-      // serves m x as many witnesses; its kernels are latency-bound, so they take about as long)
-      static const int wg = getenv("ZKFL_WIT_GROUP") ? std::max(1, atoi(getenv("ZKFL_WIT_GROUP"))) : 1;
-      pk.G = (size_t)k->max_slots * wg;
+      // one group = the proofs a key holds in flight: the witness sets' reuse (enqueue_group)
+      // relies on a group being no smaller
+      pk.G = (size_t)k->max_slots;
       ks.push_back(pk);
     }
     kidx[i] = c;
@@ -887,10 +883,10 @@ int full_prove_piped(zkfl_ctx* ctx, size_t n, KeyOf key_of, ProgOf prog_of, GetI
   }
   uint8_t* pin_out = nullptr;
   HIP_TRY(hipHostMalloc(&pin_out, off[n] + 16), "pinned witness outputs");
-  // groups enqueued ahead of the one the slots start (ZKFL_WIT_AHEAD, 1..WIT_SETS - 2): a group
-  // is computed while the slots run the `ahead` groups before it
-  static const size_t ahead = (size_t)std::clamp(getenv("ZKFL_WIT_AHEAD") ? atoi(getenv("ZKFL_WIT_AHEAD")) : 2, 1,
-                                                 WIT_SETS - 2);
+  // groups enqueued ahead of the one the slots start (1..WIT_SETS - 2): a group is computed
+  // while the slots run the `ahead` groups before it
+  constexpr size_t ahead = 2;
+  static_assert(ahead >= 1 && ahead <= WIT_SETS - 2, "a witness set is reused WIT_SETS groups later");
   auto enqueue_group = [&](PerKey& pk, size_t g) -> int {
     WitPipe* P = pk.pipe;
     WitPipe::Set& b = P->set[g % WIT_SETS];
@@ -1142,7 +1138,7 @@ int zkfl_debug_prove_parts(zkfl_ctx* ctx, zkfl_key* key, const uint8_t* wtns, si
   if (rc == ZKFL_OK) {
     s->out_proof = nullptr;
     s->out_part = nullptr;
-    rc = enqueue_proof(ctx, key, s, w->d, zeros, 1);
+    rc = enqueue_proof(ctx, key, s, w->d, zeros, ProofMode::Parts, false);
   }
   if (rc == ZKFL_OK) rc = wait_slot(s);
   hipStream_t st = s ? s->st_main : ctx->st;

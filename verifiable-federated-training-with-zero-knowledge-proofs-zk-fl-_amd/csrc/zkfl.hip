@@ -24,6 +24,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -251,6 +252,16 @@ int zkfl_ctx_create(int device, zkfl_ctx** out) {
   HIP_TRY(hipSetDevice(device), "hipSetDevice");
   zkfl_ctx* ctx = new zkfl_ctx();
   ctx->device = device;
+  // the scheduler's options (SchedOpts): the environment is read here only
+  auto env = [](const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+  };
+  ctx->opts.graph = env("ZKFL_GRAPH", 1) != 0;
+  ctx->opts.stagger = env("ZKFL_STAGGER", 1) != 0;
+  ctx->opts.lowlat = env("ZKFL_LOWLAT", 1) != 0;
+  ctx->opts.fast_wsum = env("ZKFL_FAST_WSUM", 1) != 0;
+  ctx->opts.small_logn = env("ZKFL_SMALL_LOGN", 16);
   hipError_t e = hipStreamCreateWithFlags(&ctx->st, hipStreamNonBlocking);
   if (e != hipSuccess) {
     delete ctx;
