@@ -70,7 +70,7 @@ int zkfl_ctx_destroy(zkfl_ctx* ctx);
  * stream, so with one slot every kernel runs alone and its events time it in isolation). */
 int zkfl_ctx_set_profiling(zkfl_ctx* ctx, int enabled);
 /* name: "msm_accumulate_g1", "msm_accumulate_g2", "ntt", "abc", "prove", "witness" (full-prove
- * slots).  Synchronises the device.
+ * slots), "r1cs_terms", "r1cs_verdict" (the witness check's two passes).  Synchronises the device.
  * total_ms: summed event time; units: summed algorithmic units (MSM entries, NTT elements...);
  * median_ms (nullable): median single-launch time, robust to a one-off stalled dispatch. */
 int zkfl_ctx_profile(zkfl_ctx* ctx, const char* name, double* total_ms, uint64_t* launches, double* units,
@@ -253,6 +253,45 @@ int zkfl_groth16_full_prove_json_batch(zkfl_ctx* ctx, zkfl_key* key, const zkfl_
 int zkfl_groth16_full_prove_multi(zkfl_ctx* ctx, size_t n, zkfl_key* const* keys, const zkfl_wprog* const* progs,
                                   const uint8_t* const* inputs, const uint8_t* rs, uint8_t* proofs_out,
                                   uint8_t* const* pubs_out);
+
+/* Witness check (replaces `snarkjs wtns check <circuit.r1cs> <witness.wtns>`, alias `wchk`): does
+ * every constraint <A_j, w> * <B_j, w> == <C_j, w> hold over Fr?  A Groth16 zkey carries no C
+ * matrix and the prover forms c as a * b, so zkfl_groth16_prove returns a proof for any witness;
+ * this is the call that tells a bad one apart, and names the constraint.  The .r1cs is the file the
+ * reference hands to `groth16 setup <c.r1cs> ...` (tests/full_system_simulation.mjs:713-716) and the
+ * witness is what its calculator writes (`generate_witness.cjs`, :758-767).
+ *
+ * zkfl_r1cs_header: the counts of the file's header section; n_terms counts every term of the
+ * constraints section.  zkfl_r1cs_report: n_failed = constraints that do not hold, first = the
+ * lowest such index, a, b, c = the std-form values of <A, w>, <B, w>, <C, w> at `first` (first, a, b,
+ * c are valid when n_failed > 0).  A witness whose wire 0 is not 1 fails as a whole: n_failed = 1,
+ * first = 0xFFFFFFFF, a, b, c zero.
+ *
+ * Parsing validates the whole file (iden3 r1cs v1, BN254 r; ZKFL_E_FORMAT / ZKFL_E_PRIME) and needs
+ * no device; loading makes the three matrices device-resident as one CSR term array (A rows, B rows,
+ * C rows) with scratch for one check, so one object serves one check at a time.  The check calls
+ * take n witnesses -- .wtns images, or the prover's device-resident witnesses, which are never
+ * copied to the host -- and return ZKFL_OK when every witness satisfies the system, otherwise
+ * ZKFL_E_CONSTRAINT with a message naming the lowest failing witness index and its first
+ * constraint; reports (nullable, n entries) is filled in both cases.  A witness of another length
+ * than n_wires gives ZKFL_E_MISMATCH, a value >= r ZKFL_E_ARG, both before any check runs. */
+typedef struct zkfl_r1cs zkfl_r1cs;
+typedef struct {
+  uint32_t n_wires, n_pub_out, n_pub_in, n_prv_in, n_constraints;
+  uint64_t n_labels, n_terms;
+} zkfl_r1cs_header;
+typedef struct {
+  uint32_t n_failed, first;
+  uint8_t a[32], b[32], c[32];
+} zkfl_r1cs_report;
+int zkfl_r1cs_parse(const uint8_t* buf, size_t len, zkfl_r1cs_header* out);
+int zkfl_r1cs_load(zkfl_ctx* ctx, const uint8_t* buf, size_t len, zkfl_r1cs** out);
+int zkfl_r1cs_info(const zkfl_r1cs* r1cs, zkfl_r1cs_header* out);
+int zkfl_r1cs_free(zkfl_r1cs* r1cs);
+int zkfl_r1cs_check(zkfl_ctx* ctx, const zkfl_r1cs* r1cs, size_t n, const uint8_t* const* wtns, const size_t* wtns_len,
+                    zkfl_r1cs_report* reports);
+int zkfl_r1cs_check_resident(zkfl_ctx* ctx, const zkfl_r1cs* r1cs, size_t n, const zkfl_witness* const* w,
+                             zkfl_r1cs_report* reports);
 
 /* Verification (replaces `snarkjs groth16 verify <vkey> <public> <proof>`,
  * tests/full_system_simulation.mjs:865-868; snarkjs groth16_verify, restated in

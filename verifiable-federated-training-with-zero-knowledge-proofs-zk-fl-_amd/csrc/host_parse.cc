@@ -1,5 +1,6 @@
 // Host-side parsers (see host_parse.h).  Formats: SURVEY.md Appendix A (iden3 binfile, snarkjs .wtns
-// v2 and groth16 .zkey, as `snarkjs groth16 prove` reads them, tests/full_system_simulation.mjs:773-776),
+// v2 and groth16 .zkey, as `snarkjs groth16 prove` reads them, tests/full_system_simulation.mjs:773-776;
+// circom's .r1cs as `snarkjs groth16 setup` and `snarkjs wtns check` read it, :713-716),
 // zkfl/wprog.py's witness-program image, and circom's input.json (generate_witness.cjs, :758-767).
 #include "host_parse.h"
 
@@ -514,6 +515,113 @@ int zkey_parse(const uint8_t* buf, size_t len, ZkeyHost& z, std::string& err) {
   if (s[4].size != 4 + (size_t)ncoef * 44) return bad(err, ZKFL_E_FORMAT, "zkey: coefficient section size");
   z.ncoef = ncoef;
   return coef_csr(cs + 4, ncoef, z, err);
+}
+
+// .r1cs: one validating walk over section 2 that counts each row's terms, then (csr) a second
+// walk that scatters them -- the file interleaves A_j, B_j, C_j, the rows are grouped by matrix.
+int r1cs_parse(const uint8_t* buf, size_t len, bool csr, R1csHost& o, std::string& err) {
+  std::vector<Section> s;
+  int rc = binfile_sections(buf, len, "r1cs", s, err);
+  if (rc) return rc;
+  if (rd32(buf + 4) != 1) return bad(err, ZKFL_E_FORMAT, "r1cs: unsupported version");
+  if (!s[1].present || !s[2].present) return bad(err, ZKFL_E_FORMAT, "r1cs: missing section 1 or 2");
+  // n8 | prime | nWires nPubOut nPubIn nPrvIn | nLabels u64 | mConstraints
+  if (s[1].size < 4) return bad(err, ZKFL_E_FORMAT, "r1cs: truncated header");
+  const uint8_t* h = buf + s[1].off;
+  if (rd32(h) != 32) return bad(err, ZKFL_E_FORMAT, "r1cs: n8 != 32");
+  if (s[1].size < 4 + 32) return bad(err, ZKFL_E_FORMAT, "r1cs: truncated header");
+  if (memcmp(h + 4, R_LIMBS, 32) != 0) return bad(err, ZKFL_E_PRIME, "r1cs: prime is not bn128 r");
+  if (s[1].size < 64) return bad(err, ZKFL_E_FORMAT, "r1cs: truncated header");
+  o.n_wires = rd32(h + 36);
+  o.n_pub_out = rd32(h + 40);
+  o.n_pub_in = rd32(h + 44);
+  o.n_prv_in = rd32(h + 48);
+  memcpy(&o.n_labels, h + 52, 8);
+  o.m = rd32(h + 60);
+  if (1ull + o.n_pub_out + o.n_pub_in + o.n_prv_in > o.n_wires)
+    return bad(err, ZKFL_E_FORMAT, "r1cs: signal counts exceed nWires");
+  // a constraint is at least its three term counts (12 B): m is bounded before it sizes rowptr
+  if (o.m > s[2].size / 12) return bad(err, ZKFL_E_FORMAT, "r1cs: truncated constraint");
+  const size_t m = o.m;
+  std::vector<uint32_t>& rp = o.rowptr;
+  rp.assign(3 * m + 1, 0);
+  uint64_t total = 0;
+  {
+    Reader R{buf + s[2].off, s[2].size};
+    for (size_t j = 0; j < m; j++)
+      for (size_t k = 0; k < 3; k++) {
+        const uint32_t nt = R.u32();
+        // a term is 36 B: nt is bounded by what is left before anything is read for it
+        if (!R.ok || nt > R.left / 36) return bad(err, ZKFL_E_FORMAT, "r1cs: truncated constraint");
+        const uint8_t* t = R.take(36ull * nt);
+        for (uint32_t i = 0; i < nt; i++, t += 36) {
+          uint32_t v[8];
+          memcpy(v, t + 4, 32);
+          if (rd32(t) >= o.n_wires || !fr_lt_r(v))
+            return bad(err, ZKFL_E_FORMAT, "r1cs: wire index or coefficient out of range");
+        }
+        rp[k * m + j] = nt;
+        total += nt;
+      }
+    if (R.left != 0) return bad(err, ZKFL_E_FORMAT, "r1cs: trailing bytes in the constraints section");
+  }
+  if (total >= (1ull << 32)) return bad(err, ZKFL_E_FORMAT, "r1cs: 2^32 or more terms");
+  if (s[3].present && s[3].size != 8ull * o.n_wires) return bad(err, ZKFL_E_FORMAT, "r1cs: wire2label size mismatch");
+  o.n_terms = total;
+  if (!csr) {
+    rp.clear();
+    return ZKFL_OK;
+  }
+  uint32_t run = 0;  // counts -> row starts; rp[3 m] = total
+  for (size_t r = 0; r < 3 * m; r++) {
+    const uint32_t c = rp[r];
+    rp[r] = run;
+    run += c;
+  }
+  rp[3 * m] = run;
+  uint32_t colbits = 1;
+  while (colbits < 32 && (1ull << colbits) < o.n_wires) colbits++;
+  const uint64_t id_limit = colbits < 32 ? std::min<uint64_t>(1ull << (32 - colbits), ZK_COEF_DICT_MAX) : 0;
+  const size_t K = (size_t)total;
+  std::vector<uint32_t> cols(K), ids(id_limit ? K : 0), wide;
+  CoefDict dict;
+  bool packed = id_limit != 0;
+  // validated above: these walks need no checks.  fill = false: columns and dictionary ids;
+  // fill = true (too many distinct values for the spare bits): every term keeps its coefficient
+  auto walk = [&](bool fill) {
+    const uint8_t* t = buf + s[2].off;
+    for (size_t j = 0; j < m; j++)
+      for (size_t k = 0; k < 3; k++) {
+        const uint32_t nt = rd32(t);
+        t += 4;
+        uint32_t pos = rp[k * m + j];
+        for (uint32_t i = 0; i < nt; i++, t += 36, pos++) {
+          if (fill) {
+            memcpy(&wide[(size_t)pos * 8], t + 4, 32);
+            continue;
+          }
+          cols[pos] = rd32(t);
+          if (packed) {
+            ids[pos] = dict.intern(t + 4);
+            packed = dict.size() <= id_limit;
+          }
+        }
+      }
+  };
+  walk(false);
+  if (packed) {
+    for (size_t q = 0; q < K; q++) cols[q] |= ids[q] << colbits;
+  } else {
+    wide.resize(K * 8);
+    walk(true);
+  }
+  o.cshift = packed ? colbits : 0;
+  o.cols.swap(cols);
+  if (packed)
+    o.coefs.swap(dict.vals);
+  else
+    o.coefs.swap(wide);
+  return ZKFL_OK;
 }
 
 int wprog_signals(const uint8_t* img, size_t len, std::vector<WSignal>& sigs, std::string& err) {

@@ -1,8 +1,8 @@
 // Host-side parsers of everything the C ABI accepts as bytes or text: the iden3 binfile container,
-// snarkjs .wtns and groth16 .zkey, the witness-program image written by
+// snarkjs .wtns, groth16 .zkey and circom .r1cs, the witness-program image written by
 // zkfl/wprog.py, and circom's input.json.  Pure C++ (no HIP): libzkfl links it, and
-// tools/parse_fuzz.cc links the same file under AddressSanitizer/UBSan for the corpus test
-// (tests/test_parse_fuzz.py).
+// tools/parse_fuzz.cc and tools/r1cs_fuzz.cc link the same file under AddressSanitizer/UBSan for
+// the corpus tests (tests/test_parse_fuzz.py, tests/test_r1cs_parse_cpu.py).
 //
 // Every reader checks a length before it reads: offsets are compared as `need > len - off` (never
 // `off + need > len`, which wraps for a crafted 64-bit size), counts taken from a file are bounded
@@ -49,6 +49,21 @@ struct ZkeyHost {
   uint32_t cshift = 0;           // 0 = wide terms
 };
 int zkey_parse(const uint8_t* buf, size_t len, ZkeyHost& out, std::string& err);
+
+// iden3 .r1cs v1 (the format zkfl/r1cs_file.py documents; it rejects what read_r1cs rejects):
+// section 1 header, section 2 constraints, optional section 3 wire-to-label map of nWires x u64.
+// With csr: the constraints as CSR rows over one term array -- the A rows, then the B rows, then
+// the C rows, terms in file order (zero coefficients and repeated wires kept as they are) -- in
+// zkey_parse's term encoding, coefficients std form as the file stores them.
+struct R1csHost {
+  uint32_t n_wires = 0, n_pub_out = 0, n_pub_in = 0, n_prv_in = 0, m = 0;
+  uint64_t n_labels = 0, n_terms = 0;  // n_terms: every term of the file, < 2^32
+  std::vector<uint32_t> rowptr;  // [3 m + 1]
+  std::vector<uint32_t> cols;    // packed terms (col | dict index << cshift) or plain columns
+  std::vector<uint32_t> coefs;   // dictionary (packed) or one coefficient per term, 8 u32 each
+  uint32_t cshift = 0;           // 0 = wide terms
+};
+int r1cs_parse(const uint8_t* buf, size_t len, bool csr, R1csHost& out, std::string& err);
 
 // ---------------------------------------------------------------------------
 // Witness-program image (zkfl/wprog.py, "zkwp" v2)

@@ -41,6 +41,27 @@ struct ProofStart {
 // words of the slot's pinned r | s | GLV halves, copied to the device by k_proof_start
 constexpr int RS_WORDS = (64 + 4 * (int)sizeof(GlvScalar)) / 4;
 
+// Row r of a segmented sum left by k_abc_chunks (device code; shared by k_abc_rows and the
+// constraint check, csrc/r1cs_check.hip): the chunk partials head / tail and the rows written
+// whole to abc, stitched over the chunks the row spans.
+__device__ __forceinline__ Fr abc_row(const uint32_t* __restrict__ rp, uint32_t r, uint32_t K,
+                                      const Fr* __restrict__ head, const Fr* __restrict__ tail,
+                                      const Fr* __restrict__ abc) {
+  const uint32_t s = rp[r], e = rp[r + 1];
+  if (s == e) return fp_zero<FrP>();
+  const uint32_t c0 = s / ABC_L, c1 = (e - 1) / ABC_L;
+  const bool starts = (s == c0 * ABC_L);
+  if (c0 == c1) {
+    const uint32_t cend = (c0 + 1) * ABC_L < K ? (c0 + 1) * ABC_L : K;
+    if (starts) return head[c0];
+    if (e == cend) return tail[c0];
+    return abc[r];  // wholly inside the chunk: written by k_abc_chunks
+  }
+  Fr acc = starts ? head[c0] : tail[c0];
+  for (uint32_t c = c0 + 1; c <= c1; c++) acc = fp_add(acc, head[c]);
+  return acc;
+}
+
 // k_abc_chunks over the K terms (packed when T.cshift != 0), K > 0
 void abc_chunks(hipStream_t st, const uint32_t* rp, uint32_t nrows, const AbcTerms& T, const Fr* w, uint32_t K,
                 Fr* head, Fr* tail, Fr* abc);

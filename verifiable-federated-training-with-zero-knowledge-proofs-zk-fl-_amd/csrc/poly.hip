@@ -80,24 +80,7 @@ __global__ void __launch_bounds__(64) k_abc_chunks(const uint32_t* __restrict__ 
   else tail[c] = acc;
 }
 
-__device__ __forceinline__ Fr abc_row(const uint32_t* __restrict__ rp, uint32_t r, uint32_t K,
-                                      const Fr* __restrict__ head, const Fr* __restrict__ tail,
-                                      const Fr* __restrict__ abc) {
-  const uint32_t s = rp[r], e = rp[r + 1];
-  if (s == e) return fp_zero<FrP>();
-  const uint32_t c0 = s / ABC_L, c1 = (e - 1) / ABC_L;
-  const bool starts = (s == c0 * ABC_L);
-  if (c0 == c1) {
-    const uint32_t cend = (c0 + 1) * ABC_L < K ? (c0 + 1) * ABC_L : K;
-    if (starts) return head[c0];
-    if (e == cend) return tail[c0];
-    return abc[r];  // wholly inside the chunk: written by k_abc_chunks
-  }
-  Fr acc = starts ? head[c0] : tail[c0];
-  for (uint32_t c = c0 + 1; c <= c1; c++) acc = fp_add(acc, head[c]);
-  return acc;
-}
-
+// (abc_row, the row stitching over head / tail / abc: poly.h)
 __global__ void __launch_bounds__(256) k_abc_rows(const uint32_t* __restrict__ rp, size_t n, uint32_t K,
                                                   const Fr* __restrict__ head, const Fr* __restrict__ tail,
                                                   Fr* __restrict__ abc) {

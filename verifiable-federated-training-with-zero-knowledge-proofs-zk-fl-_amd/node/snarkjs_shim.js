@@ -253,9 +253,21 @@ async function r1csInfo(r1csFile) {
   };
 }
 
+// snarkjs wtns.check(r1csFileName, wtnsFileName) -> true / false: the Python host's `wtns check`
+// (libzkfl zkfl_r1cs_check) as a child process, its report on this process's stderr.
+function wtnsCheck(r1csFile, wtnsFile) {
+  return new Promise((resolve, reject) => {
+    const c = require('child_process').spawn(process.env.ZKFL_PYTHON || 'python3',
+      ['-m', 'zkfl', 'wtns', 'check', r1csFile, wtnsFile], { stdio: ['ignore', 'ignore', 'inherit'], env: hostEnv() });
+    c.on('error', reject);
+    c.on('exit', (code) => (code === 0 || code === 1 ? resolve(code === 0)
+      : reject(new Error('wtns check: the zkfl host exited with status ' + code))));
+  });
+}
+
 module.exports = {
   groth16: { prove, fullProve, verify },
-  wtns: { calculate: wtnsCalculate },
+  wtns: { calculate: wtnsCalculate, check: wtnsCheck },
   zKey: { exportVerificationKey },
   r1cs: { info: r1csInfo },
   addon, proofToJson, vkBuffer,
@@ -282,20 +294,25 @@ function done(p) {
 // tests/full_system_simulation.mjs:713-730) are served by the package's Python host, which drives
 // the same libzkfl (zkfl_setup_*: scalar multiplications, group FFTs and sparse combinations on the
 // GPU): `python3 -m zkfl <the same argv>` as a child process, its exit status passed through.
-const CEREMONY = new Set(['powersoftau', 'ptn', 'ptc', 'pt2', 'g16s', 'zkn', 'zkc']);
+// `wtns check <c.r1cs> <w.wtns>` (alias wchk) goes the same way: the addon has no binding of its own.
+const CEREMONY = new Set(['powersoftau', 'ptn', 'ptc', 'pt2', 'g16s', 'zkn', 'zkc', 'wchk']);
 
 function isCeremony(argv) {
   const a = argv.filter((x) => !x.startsWith('-'));
-  return CEREMONY.has(a[0]) || (a[0] === 'groth16' && a[1] === 'setup') ||
+  return CEREMONY.has(a[0]) || (a[0] === 'groth16' && a[1] === 'setup') || (a[0] === 'wtns' && a[1] === 'check') ||
     (a[0] === 'zkey' && (a[1] === 'new' || a[1] === 'contribute'));
+}
+
+function hostEnv() {
+  const pkg = path.join(__dirname, '..');
+  return Object.assign({}, process.env, {
+    PYTHONPATH: pkg + (process.env.PYTHONPATH ? path.delimiter + process.env.PYTHONPATH : ''),
+  });
 }
 
 function runCeremony(argv) {
   const { spawnSync } = require('child_process');
-  const pkg = path.join(__dirname, '..');
-  const env = Object.assign({}, process.env, {
-    PYTHONPATH: pkg + (process.env.PYTHONPATH ? path.delimiter + process.env.PYTHONPATH : ''),
-  });
+  const env = hostEnv();
   const r = spawnSync(process.env.ZKFL_PYTHON || 'python3', ['-m', 'zkfl'].concat(argv), { stdio: 'inherit', env });
   if (r.error) {
     console.error('[ERROR] snarkJS: cannot start the zkfl ceremony host: ' + r.error.message);
@@ -349,6 +366,7 @@ if (require.main === module && isCeremony(process.argv.slice(2))) {
                   '       snarkjs groth16 fullprove <input.json> <circuit.wasm> <zkey> <proof.json> <public.json>\n' +
                   '       snarkjs groth16 verify <vkey.json> <public.json> <proof.json>\n' +
                   '       snarkjs wtns calculate <circuit.wasm> <input.json> <out.wtns>\n' +
+                  '       snarkjs wtns check <circuit.r1cs> <witness.wtns>\n' +
                   '       snarkjs zkey export verificationkey <zkey> <vkey.json>\n' +
                   '       snarkjs r1cs info <circuit.r1cs>\n' +
                   '       snarkjs powersoftau new bn128 <power> <out.ptau>\n' +

@@ -15,7 +15,10 @@
                                                              DEVELOPMENT ceremony: fresh random toxic waste, discarded
     python -m zkfl export-vk <zkey> <vkey.json>              snarkjs zkey export verificationkey
     python -m zkfl wtns <circuit.zkwp> <input.json> <out.wtns>              generate_witness.cjs (:758-767)
-    python -m zkfl prove <zkey> <wtns> <proof.json> <public.json>           snarkjs groth16 prove (:773-776)
+    python -m zkfl wtns check <circuit.r1cs> <witness.wtns>                 snarkjs wtns check (alias: wchk); exit 1
+                                                                            and the first failing constraint otherwise
+    python -m zkfl prove <zkey> <wtns> <proof.json> <public.json> [--r1cs <circuit.r1cs>]   snarkjs groth16 prove
+        (:773-776); --r1cs: check the witness first, exit 1 without writing a proof when it fails
     python -m zkfl verify <vkey.json> <public.json> <proof.json>            snarkjs groth16 verify (:865-868)
 
 <circuit> is one of zkfl.circuits.CIRCUITS (poseidon_hash2, sgd_verified, sgd_step_v5,
@@ -136,8 +139,10 @@ def cmd_wtns(args):
 
 def cmd_prove(args):
     p = groth16.Prover(int(os.environ.get("LOCAL_RANK", "0")))
-    proof, public = p.prove(args.zkey, args.wtns)
-    p.close()
+    try:
+        proof, public = p.prove(args.zkey, args.wtns, r1cs=args.r1cs)
+    finally:
+        p.close()
     with open(args.proof, "w") as f:
         json.dump(proof, f, indent=1)
     with open(args.public, "w") as f:
@@ -157,7 +162,7 @@ def cmd_verify(args):
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
-    if argv and argv[0] in snarkjs_cli.VERBS:   # snarkjs ceremony strings (zkfl/snarkjs_cli.py)
+    if snarkjs_cli.routes(argv):   # snarkjs ceremony strings and `wtns check` (zkfl/snarkjs_cli.py)
         return snarkjs_cli.run(argv)
     ap = argparse.ArgumentParser(prog="python -m zkfl", description=__doc__.split("\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -191,6 +196,7 @@ def main(argv=None):
     sp = sub.add_parser("prove")
     for a in ("zkey", "wtns", "proof", "public"):
         sp.add_argument(a)
+    sp.add_argument("--r1cs", default=None, help="check the witness against this .r1cs before proving")
     sp = sub.add_parser("verify")
     for a in ("vkey", "public", "proof"):
         sp.add_argument(a)

@@ -7,6 +7,7 @@ Mirrors the snarkjs API/CLI the reference harness drives:
   ``export_verification_key(zkey)``        <- ``snarkjs zkey export verificationkey`` (:732-735)
   ``r1cs_info(circuit)``                   <- ``snarkjs r1cs info`` (tests/test_verified_gradient.mjs:351-356)
   ``verify(vkey, public, proof)``          <- ``snarkjs groth16 verify`` (:865-868), on the GPU
+  ``wtns_check(r1cs, wtns)``               <- ``snarkjs wtns check <c.r1cs> <w.wtns>`` (snarkjs ``wtns.check``), on the GPU
 Outputs are snarkjs's JSON shapes: proof.json = {pi_a, pi_b, pi_c, protocol, curve} with
 decimal strings, public.json = list of decimal strings (witness[1..nPublic]).
 """
@@ -154,9 +155,16 @@ class Prover:
             self._keys[digest] = k
         return k
 
-    def prove(self, zkey, wtns, rs: bytes | None = None):
-        """-> (proof.json dict, public.json list)"""
-        proof, pub = self.key(zkey).prove(_read(wtns), rs)
+    def prove(self, zkey, wtns, rs: bytes | None = None, r1cs=None):
+        """-> (proof.json dict, public.json list).  r1cs (bytes or path): the witness is checked
+        against it first, and one that does not satisfy it raises ZkflError(ZKFL_E_CONSTRAINT)
+        instead of yielding a proof that cannot verify."""
+        wtns = _read(wtns)
+        if r1cs is not None:
+            with native.R1cs(self.ctx, _read(r1cs)) as cs:
+                if not cs.check([wtns], reports=False):
+                    raise native.ZkflError(-7, cs.last_error)
+        proof, pub = self.key(zkey).prove(wtns, rs)
         return proof_to_json(proof), [str(x) for x in pub]
 
     def full_prove(self, inputs: dict, circuit, zkey, rs: bytes | None = None):
@@ -190,8 +198,22 @@ def _prover() -> Prover:
     return _default
 
 
-def prove(zkey, wtns, rs: bytes | None = None):
-    return _prover().prove(zkey, wtns, rs)
+def prove(zkey, wtns, rs: bytes | None = None, r1cs=None):
+    return _prover().prove(zkey, wtns, rs, r1cs=r1cs)
+
+
+def wtns_check_report(r1cs, wtns, ctx: native.Context | None = None) -> native.Report:
+    """The witness (.wtns bytes or path) against the circuit's .r1cs (bytes or path) -> the check's
+    report: n_failed, the first failing constraint and its a, b, c values."""
+    with native.R1cs(ctx or _prover().ctx, _read(r1cs)) as cs:
+        return cs.check([_read(wtns)])[0]
+
+
+def wtns_check(r1cs, wtns, ctx: native.Context | None = None) -> bool:
+    """snarkjs ``wtns.check(r1csFileName, wtnsFileName)`` -> bool: every constraint of the .r1cs
+    holds for the witness (checked on the GPU).  A malformed file, or a witness of another length
+    than the circuit's wires, raises ZkflError."""
+    return wtns_check_report(r1cs, wtns, ctx).ok
 
 
 def fullProve(inputs: dict, circuit, zkey, rs: bytes | None = None):  # noqa: N802 (snarkjs name)
@@ -204,4 +226,5 @@ def verify(vk: dict, public, proof: dict) -> bool:
 
 
 __all__ = ["prove", "fullProve", "verify", "Prover", "proof_to_json", "proof_from_json", "export_verification_key",
-           "vk_bytes", "public_bytes", "wtns_calculate", "r1cs_info", "read_wtns"]
+           "vk_bytes", "public_bytes", "wtns_calculate", "r1cs_info", "read_wtns", "wtns_check",
+           "wtns_check_report"]

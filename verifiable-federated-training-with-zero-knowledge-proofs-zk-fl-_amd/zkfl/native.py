@@ -24,9 +24,27 @@ ERRORS = {
     -5: "ZKFL_E_DEVICE", -6: "ZKFL_E_OOM", -7: "ZKFL_E_CONSTRAINT",
 }
 
-# every exported symbol of include/zkfl.h with (restype, argtypes)
 _P = C.c_void_p
 _U8P = C.POINTER(C.c_uint8)
+
+
+class R1csHeader(C.Structure):
+    """zkfl_r1cs_header: the counts of a .r1cs (n_terms: every term of its constraints section)."""
+    _fields_ = [("n_wires", C.c_uint32), ("n_pub_out", C.c_uint32), ("n_pub_in", C.c_uint32),
+                ("n_prv_in", C.c_uint32), ("n_constraints", C.c_uint32), ("n_labels", C.c_uint64),
+                ("n_terms", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class R1csReport(C.Structure):
+    """zkfl_r1cs_report"""
+    _fields_ = [("n_failed", C.c_uint32), ("first", C.c_uint32), ("a", C.c_uint8 * 32), ("b", C.c_uint8 * 32),
+                ("c", C.c_uint8 * 32)]
+
+
+# every exported symbol of include/zkfl.h with (restype, argtypes)
 SIGNATURES = {
     "zkfl_version": (C.c_int, []),
     "zkfl_build_id": (C.c_char_p, []),
@@ -99,6 +117,13 @@ SIGNATURES = {
                                                      _U8P]),
     "zkfl_groth16_full_prove_multi": (C.c_int, [_P, C.c_size_t, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_char_p),
                                                 C.c_char_p, _U8P, C.POINTER(_U8P)]),
+    "zkfl_r1cs_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(R1csHeader)]),
+    "zkfl_r1cs_load": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(_P)]),
+    "zkfl_r1cs_info": (C.c_int, [_P, C.POINTER(R1csHeader)]),
+    "zkfl_r1cs_free": (C.c_int, [_P]),
+    "zkfl_r1cs_check": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                  C.POINTER(R1csReport)]),
+    "zkfl_r1cs_check_resident": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(_P), C.POINTER(R1csReport)]),
 }
 
 
@@ -680,3 +705,88 @@ class WitnessProgram:
         arr = (_P * max(1, n))()
         check(lib().zkfl_witness_compute_resident(self.ctx.h, self.h, key.h, n, self._inputs(inputs), arr))
         return [ResidentWitness(key, handle=_P(arr[i])) for i in range(n)]
+
+
+NO_CONSTRAINT = 0xFFFFFFFF   # Report.first of a witness whose wire 0 is not 1
+
+
+class Report:
+    """One witness's check (zkfl_r1cs_report): ``ok``; otherwise ``n_failed`` constraints do not
+    hold, ``first`` is the lowest such index and ``a``, ``b``, ``c`` the values of <A, w>, <B, w>,
+    <C, w> there (``first == NO_CONSTRAINT``: wire 0 is not 1, no constraint was looked at)."""
+
+    def __init__(self, r: R1csReport):
+        self.n_failed, self.first = int(r.n_failed), int(r.first)
+        self.a, self.b, self.c = (int.from_bytes(bytes(x), "little") for x in (r.a, r.b, r.c))
+
+    @property
+    def ok(self) -> bool:
+        return self.n_failed == 0
+
+    def __repr__(self):
+        if self.ok:
+            return "Report(ok)"
+        return f"Report(n_failed={self.n_failed}, first={self.first}, a={self.a}, b={self.b}, c={self.c})"
+
+
+def r1cs_header(r1cs: bytes) -> dict:
+    """A .r1cs validated as a whole and its header counts (zkfl_r1cs_parse; host only, no device)."""
+    h = R1csHeader()
+    check(lib().zkfl_r1cs_parse(r1cs, len(r1cs), C.byref(h)))
+    return h.as_dict()
+
+
+class R1cs:
+    """A circuit's .r1cs on the device, to check witnesses against (`snarkjs wtns check`)."""
+
+    def __init__(self, ctx: Context, r1cs: bytes):
+        h = _P()
+        check(lib().zkfl_r1cs_load(ctx.h, r1cs, len(r1cs), C.byref(h)))
+        self.h, self.ctx = h, ctx
+        ctx._own(self)
+
+    def close(self):
+        if self.h:
+            lib().zkfl_r1cs_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def info(self) -> dict:
+        h = R1csHeader()
+        check(lib().zkfl_r1cs_info(self.h, C.byref(h)))
+        return h.as_dict()
+
+    def _finish(self, rc, reps, n, reports):
+        """-> the n reports; with reports=False the call's verdict alone (True: all satisfied)."""
+        if rc not in (ZKFL_OK, -7):
+            check(rc)
+        self.last_error = lib().zkfl_last_error().decode(errors="replace") if rc else ""
+        return [Report(reps[i]) for i in range(n)] if reports else rc == ZKFL_OK
+
+    def check(self, wtns_list, reports: bool = True):
+        """.wtns images -> [Report] (one batch, one copy back); a malformed witness, one of another
+        length or with a value >= r raises ZkflError.  ``last_error`` keeps the library's message,
+        which names the lowest failing witness and its first constraint."""
+        n = len(wtns_list)
+        arr = (C.c_char_p * max(1, n))(*wtns_list)
+        lens = (C.c_size_t * max(1, n))(*[len(w) for w in wtns_list])
+        reps = (R1csReport * max(1, n))() if reports else None
+        return self._finish(lib().zkfl_r1cs_check(self.ctx.h, self.h, n, arr, lens, reps), reps, n, reports)
+
+    def check_resident(self, ws, reports: bool = True):
+        """The same for device-resident witnesses (ProvingKey.upload, WitnessProgram.compute_resident)."""
+        n = len(ws)
+        arr = (_P * max(1, n))(*[w.h for w in ws])
+        reps = (R1csReport * max(1, n))() if reports else None
+        return self._finish(lib().zkfl_r1cs_check_resident(self.ctx.h, self.h, n, arr, reps), reps, n, reports)

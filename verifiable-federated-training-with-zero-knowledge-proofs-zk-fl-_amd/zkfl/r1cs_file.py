@@ -125,12 +125,13 @@ def read_r1cs(buf: bytes) -> R1csFile:
         cons.append(tuple(lcs))
     if c.off != c.end:
         raise ValueError("r1cs: trailing bytes in the constraints section")
-    wire2label = list(range(n_wires))
     if 3 in secs:
         lr = _Reader(buf, *secs[3])
-        if lr.end - lr.off != 8 * n_wires:
+        if lr.end - lr.off != 8 * n_wires:   # before n_wires sizes a list: a hostile count stays cheap
             raise ValueError("r1cs: wire2label size mismatch")
         wire2label = [lr.u64() for _ in range(n_wires)]
+    else:
+        wire2label = list(range(n_wires))
     return R1csFile(n_wires, n_pub_out, n_pub_in, n_prv_in, n_labels, cons, wire2label)
 
 

@@ -8,9 +8,17 @@ Served for `python -m zkfl <snarkjs argv>` and, through it, for the Node shim's 
   groth16 setup <c.r1cs> <pot.ptau> <c_0000.zkey>     :48-57, tests/full_system_simulation.mjs:714-716
   zkey contribute <in.zkey> <out.zkey> [--name=..] [-e=..]   tests/full_system_simulation.mjs:723-726
   zkey export verificationkey <c.zkey> <vkey.json>    :732-735, tests/test_secureagg.cjs:58-64
+  wtns check <c.r1cs> <w.wtns>                        snarkjs's witness check (alias wchk)
 and the snarkjs aliases ptn, ptc, pt2, g16s, zkn (= groth16 setup), zkc, zkev.  The group work runs
 on the GPU (zkfl/ptau.py, zkfl/zkey.py -> libzkfl zkfl_setup_*).  Exit status 0 on success, 1 with
 an `[ERROR] snarkJS: ...` line otherwise (snarkjs's CLI convention).
+
+`wtns check` (libzkfl zkfl_r1cs_check) prints `[INFO]  snarkJS: WITNESS IS CORRECT` and exits 0, or
+`[ERROR] snarkJS: WITNESS IS NOT CORRECT`, the first failing constraint with its a, b, c values and
+the number of failing constraints, and exits 1.  snarkjs was not available to compare with, so that
+wording and the exit status of a failed check are this module's choice, not pinned to snarkjs's
+(as DESIGN.md §3 says of the other conventions).  `python -m zkfl` routes only `wtns check` here:
+`wtns <program> <input> <out>` stays its own witness-generation subcommand.
 """
 
 from __future__ import annotations
@@ -20,7 +28,7 @@ import os
 import sys
 
 VERBS = ("powersoftau", "ptn", "ptc", "pt2", "groth16", "g16s", "zkey", "zkn", "zkc", "zkev")
-ALIASES = {"ptn": ["powersoftau", "new"], "ptc": ["powersoftau", "contribute"],
+ALIASES = {"wchk": ["wtns", "check"], "ptn": ["powersoftau", "new"], "ptc": ["powersoftau", "contribute"],
            "pt2": ["powersoftau", "prepare", "phase2"], "g16s": ["groth16", "setup"], "zkn": ["groth16", "setup"],
            "zkc": ["zkey", "contribute"], "zkev": ["zkey", "export", "verificationkey"]}
 
@@ -66,11 +74,39 @@ def _write(path, data):
         f.write(data)
 
 
+def routes(argv) -> bool:
+    """Is this argv one of the snarkjs strings served here?  (`wtns` alone is not: only `wtns check`.)"""
+    return bool(argv) and (argv[0] in VERBS or argv[0] == "wchk" or list(argv[:2]) == ["wtns", "check"])
+
+
+def wtns_check(r1cs_path, wtns_path) -> int:
+    from . import native
+    with _ctx() as ctx, native.R1cs(ctx, _read(r1cs_path)) as cs:
+        rep = cs.check([_read(wtns_path)])[0]
+        m = cs.info()["n_constraints"]
+    if rep.ok:
+        _info("WITNESS IS CORRECT")
+        return 0
+    err = lambda msg: print(f"[ERROR] snarkJS: {msg}", file=sys.stderr)  # noqa: E731
+    err("WITNESS IS NOT CORRECT")
+    if rep.first == native.NO_CONSTRAINT:
+        err("wire 0 is not 1")
+        return 1
+    err(f"first failing constraint: #{rep.first}")
+    err(f"a = {rep.a}")
+    err(f"b = {rep.b}")
+    err(f"c = {rep.c}")
+    err(f"{rep.n_failed} of {m} constraints fail")
+    return 1
+
+
 def run(argv) -> int:
     from . import groth16, ptau, r1cs_file, zkey
     pos, opts = parse(argv)
     try:
-        if pos[:2] == ["powersoftau", "new"] and len(pos) >= 5:
+        if pos[:2] == ["wtns", "check"] and len(pos) >= 4:
+            return wtns_check(pos[2], pos[3])
+        elif pos[:2] == ["powersoftau", "new"] and len(pos) >= 5:
             if pos[2] not in ("bn128", "bn254", "alt_bn128"):
                 raise ValueError(f"curve not supported: {pos[2]}")
             power = int(pos[3])
@@ -116,7 +152,8 @@ def run(argv) -> int:
                   "       snarkjs powersoftau prepare phase2 <in.ptau> <out.ptau>\n"
                   "       snarkjs groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>\n"
                   "       snarkjs zkey contribute <in.zkey> <out.zkey> [--name=name] [-e=entropy]\n"
-                  "       snarkjs zkey export verificationkey <circuit.zkey> <vkey.json>", file=sys.stderr)
+                  "       snarkjs zkey export verificationkey <circuit.zkey> <vkey.json>\n"
+                  "       snarkjs wtns check <circuit.r1cs> <witness.wtns>", file=sys.stderr)
             return 99
     except (ValueError, OSError) as e:
         print(f"[ERROR] snarkJS: {e}", file=sys.stderr)
