@@ -54,6 +54,7 @@ typedef struct zkfl_ctx zkfl_ctx;
 typedef struct zkfl_key zkfl_key;
 typedef struct zkfl_witness zkfl_witness;
 typedef struct zkfl_wprog zkfl_wprog;
+typedef struct zkfl_vkey zkfl_vkey;
 
 int zkfl_version(void);
 /* First 16 hex digits of SHA-256 over the sources this library was built from (the csrc .h, .hip
@@ -70,7 +71,9 @@ int zkfl_ctx_destroy(zkfl_ctx* ctx);
  * stream, so with one slot every kernel runs alone and its events time it in isolation). */
 int zkfl_ctx_set_profiling(zkfl_ctx* ctx, int enabled);
 /* name: "msm_accumulate_g1", "msm_accumulate_g2", "ntt", "abc", "prove", "witness" (full-prove
- * slots), "r1cs_terms", "r1cs_verdict" (the witness check's two passes).  Synchronises the device.
+ * slots), "r1cs_terms", "r1cs_verdict" (the witness check's two passes), "verify_wave_g2",
+ * "verify_wave_inputs", "verify_wave_pair" (the wave verifier's three kernels; units: proofs).
+ * Synchronises the device.
  * total_ms: summed event time; units: summed algorithmic units (MSM entries, NTT elements...);
  * median_ms (nullable): median single-launch time, robust to a one-off stalled dispatch. */
 int zkfl_ctx_profile(zkfl_ctx* ctx, const char* name, double* total_ms, uint64_t* launches, double* units,
@@ -313,6 +316,41 @@ int zkfl_groth16_verify_batch(zkfl_ctx* ctx, const uint8_t* vk, size_t vk_len, s
 int zkfl_pairing(zkfl_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* gt_out);
 /* Parity hook: the Miller-loop value before the final exponentiation, same layout. */
 int zkfl_debug_miller_loop(zkfl_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2, uint8_t* out);
+
+/* Resident verification keys and a round's proofs, each against its own key (the reference's
+ * server verifies phase by phase with three keys, tests/full_system_simulation.mjs:1298-1343).
+ *
+ * The load call takes the vk image of zkfl_groth16_verify and keeps the prepared key on the
+ * device until it is freed; any number may be resident (the context's one-key cache behind
+ * zkfl_groth16_verify and its batch form is separate and untouched).  Errors: ZKFL_E_FORMAT
+ * (truncated image, wrong length, a point off its curve / outside its subgroup / at infinity).
+ * Keys with at most ZKFL_VERIFY_WAVE_MAX_PUBLIC public signals also get the wave path's
+ * per-window tables (64 KB per public signal). */
+#define ZKFL_VERIFY_WAVE_MAX_PUBLIC 32
+int zkfl_vkey_load(zkfl_ctx* ctx, const uint8_t* vk, size_t vk_len, zkfl_vkey** out);
+int zkfl_vkey_info(const zkfl_vkey* key, uint32_t* n_public);
+int zkfl_vkey_free(zkfl_vkey* key);
+
+/* Job i checks proofs + 256 i against vkeys[i] with pubs[i] (npubs[i] x 32 B); results[i] = 1 / 0
+ * by the verdict rules of zkfl_groth16_verify_batch.  npubs[i] != the key's nPublic gives
+ * ZKFL_E_MISMATCH naming the job before any device work (results untouched); an unknown schedule
+ * ZKFL_E_ARG.  The schedules compute the same verdicts:
+ *   LANES  one proof per lane: jobs grouped by key, one batch pass per key, verdicts scattered
+ *          back to job order (throughput: thousands of proofs);
+ *   WAVES  one proof per wavefront (csrc/verify_wave.hip): the latency of one proof or one round;
+ *          a job whose key exceeds ZKFL_VERIFY_WAVE_MAX_PUBLIC takes LANES;
+ *   AUTO   WAVES up to ZKFL_VERIFY_AUTO_WAVES_MAX jobs, LANES above (the measured crossover,
+ *          tools/bench_verify.py --multi). */
+#define ZKFL_VERIFY_AUTO 0
+#define ZKFL_VERIFY_LANES 1
+#define ZKFL_VERIFY_WAVES 2
+#define ZKFL_VERIFY_AUTO_WAVES_MAX 4096
+int zkfl_groth16_verify_multi(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
+                              const size_t* npubs, const uint8_t* proofs, int32_t* results, int schedule);
+/* Parity hook: zkfl_pairing (final_exp != 0) / zkfl_debug_miller_loop (final_exp == 0) computed by
+ * the wave path's tower, Miller loop and final exponentiation; same inputs, layout and errors. */
+int zkfl_debug_wave_pairing(zkfl_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2, int final_exp,
+                            uint8_t* out);
 
 /* Poseidon hashing and Merkle trees on the GPU: the reference's data/server side
  * (tests/full_system_simulation.mjs:139-238, circomlibjs `poseidon` [ext]), bit-identical to

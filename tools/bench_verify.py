@@ -4,6 +4,10 @@
 Circuit: sgd_verified(8,4,3,1000) (6 public signals), dev ceremony, one proof replicated.
 Prints one JSON line per batch size.  Not part of the bench.py contract (verification is a
 correctness gate in SURVEY.md §8 a9, not the metric).
+
+    bench_verify.py [sizes..]            one key, zkfl_groth16_verify_batch
+    bench_verify.py --multi [sizes..]    two resident keys, zkfl_groth16_verify_multi: one line per
+                                         (schedule, n), lanes and waves in the same process
 """
 import json
 import os
@@ -17,7 +21,52 @@ from zkfl import circuits, clients, groth16, native, wprog  # noqa: E402
 from zkfl import zkey  # noqa: E402
 
 
+def multi(sizes, repeats=10):
+    """--multi: a round's proofs against two resident keys, sgd_verified(8,4,3) and
+    secure_masked_update(4,7) (bench.py config 5's pair), interleaved as a round interleaves them
+    (training, secure aggregation, training, ...).  One JSON line per (schedule, n): median, min and
+    max wall time of `repeats` verify_multi calls after one warm-up call, same process, same jobs."""
+    import statistics
+    ctx = native.Context(0)
+    tr, sa, _ = clients.federated_round(8, rnd=1)[0]
+    made = []
+    for i, (b, inp) in enumerate(((circuits.build("sgd_verified", 8, 4, 3, 1000), tr),
+                                  (circuits.build("secure_masked_update", 4, 7), sa))):
+        zk = zkey.groth16_setup(b, ctx, zkey.Toxic(tau=0xC5 + i, alpha=3, beta=5, gamma=7, delta=11 + i))
+        key = native.ProvingKey(ctx, zk)
+        wp = native.WitnessProgram(ctx, wprog.compile_program(b))
+        proof, pub = key.prove(wp.compute([wprog.input_bytes(b, inp)])[0])
+        wp.close()
+        key.close()
+        vk = native.VerifyingKey(ctx, groth16.vk_bytes(groth16.export_verification_key(zk, alphabeta=False)))
+        made.append((vk, groth16.public_bytes(pub), proof))
+    for n in sizes:
+        jobs = [made[i % 2] for i in range(n)]
+        for sched in ("lanes", "waves"):
+            assert all(ctx.verify_multi(jobs, sched))  # warm-up, and the verdicts
+            ts = []
+            for _ in range(repeats):
+                t0 = time.perf_counter()
+                ctx.verify_multi(jobs, sched)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            print(json.dumps({"schedule": sched, "n": n, "median_ms": round(statistics.median(ts), 3),
+                              "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3), "repeats": repeats,
+                              "npub": [made[0][0].n_public, made[1][0].n_public],
+                              "build": native.build_id()}), flush=True)
+    # where the wave path's time goes: per-kernel event times of one proof and of a round of 16
+    for n in (1, 16):
+        ctx.set_profiling(True)
+        ctx.profile_reset()
+        ctx.verify_multi([made[i % 2] for i in range(n)], "waves")
+        prof = {k: round(ctx.profile(k)[0], 3) for k in ("verify_wave_g2", "verify_wave_inputs", "verify_wave_pair")}
+        ctx.set_profiling(False)
+        print(json.dumps({"profile_ms": prof, "n": n}), flush=True)
+    ctx.close()
+
+
 def main():
+    if "--multi" in sys.argv[1:]:
+        return multi([int(x) for x in sys.argv[1:] if x != "--multi"] or [1, 16, 64, 256, 1024, 4096])
     sizes = [int(x) for x in (sys.argv[1:] or ["1", "64", "1024", "8192"])]
     b = circuits.build("sgd_verified", 8, 4, 3, 1000)
     inp, _ = clients.Client(1, 8, 4, 3, clients.JsLcg(12345)).training_input(8, 1000, 100000000)

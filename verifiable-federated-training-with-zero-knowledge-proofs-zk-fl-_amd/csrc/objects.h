@@ -163,6 +163,15 @@ struct zkfl_wprog {
   zkfl::WProg* p = nullptr;
 };
 
+// A resident verification key (zkfl_vkey_load): the lane path's prepared key plus the wave
+// path's per-window IC tables (csrc/verify_wave.hip).
+struct zkfl_vkey {
+  zkfl_ctx* ctx = nullptr;
+  zkfl::VkDev* vk = nullptr;
+  void* wtab = nullptr;   // vk_wave_tables (null without public signals or above the cap)
+  bool wave_ok = false;   // nPublic <= ZKFL_VERIFY_WAVE_MAX_PUBLIC
+};
+
 namespace zkfl {
 void ctx_retain(zkfl_ctx* ctx);
 void ctx_release(zkfl_ctx* ctx);  // drops one reference; the last one tears the context down

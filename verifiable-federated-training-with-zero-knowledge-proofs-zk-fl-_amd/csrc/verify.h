@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "prof.h"
+
 namespace zkfl {
 
 struct VkDev;  // prepared verification key (device tables + lines), opaque
@@ -26,5 +28,24 @@ int verify_batch(const VkDev* vk, size_t n, const uint8_t* pubs, const uint8_t* 
 // (ffjavascript toObject order).  Points that are off-curve / out of G2 -> ZKFL_E_ARG.
 int pairing_batch(size_t n, const uint8_t* g1, const uint8_t* g2, int final_exp, uint8_t* out, hipStream_t st,
                   std::string& err);
+
+// ---- one proof per wavefront (csrc/verify_wave.hip) ----
+// The wave path's per-key tables d * 16^w * IC_i (64 KB per public signal, device memory); *out
+// stays null when the key has no public signal or more than ZKFL_VERIFY_WAVE_MAX_PUBLIC.
+int vk_wave_tables(const VkDev* vk, hipStream_t st, void** out, std::string& err);
+void vk_wave_tables_free(void* tab);
+
+struct VerifyJob {
+  const VkDev* vk;
+  const void* wtab;    // vk_wave_tables of vk
+  const uint8_t* pub;  // vk_npub(vk) x 32 B
+};
+// results[i] = 1 / 0 for proof i (256 B each) against jobs[i]: verify_batch's verdicts.  Every
+// job's key must be within the wave path's nPublic cap.  prof (nullable): "verify_wave_*" records.
+int verify_wave(size_t n, const VerifyJob* jobs, const uint8_t* proofs, int32_t* results, hipStream_t st,
+                Profiler* prof, std::string& err);
+// pairing_batch on the wave path's tower, Miller loop and final exponentiation.
+int pairing_wave_batch(size_t n, const uint8_t* g1, const uint8_t* g2, int final_exp, uint8_t* out, hipStream_t st,
+                       Profiler* prof, std::string& err);
 
 }  // namespace zkfl

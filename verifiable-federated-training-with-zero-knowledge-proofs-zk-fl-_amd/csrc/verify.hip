@@ -22,73 +22,12 @@
 #include "curve.h"
 #include "pairing.h"
 #include "verify.h"
+#include "verify_dev.h"
 #include "zkfl.h"
 
 namespace zkfl {
 
 namespace {
-
-constexpr uint32_t ST_INF = 1u, ST_BAD = 2u;
-
-ZK_DEV bool lt_mod(const uint32_t* v, const uint32_t* P) {
-  for (int i = 7; i >= 0; i--)
-    if (v[i] != P[i]) return v[i] < P[i];
-  return false;
-}
-
-// canonical std-form Fq -> Montgomery; false if >= q
-ZK_DEV bool fq_load_std(const uint32_t* s, Fq& out) {
-  Fq t;
-#pragma unroll
-  for (int i = 0; i < 8; i++) t.v[i] = s[i];
-  if (!lt_mod(t.v, FqP::P)) return false;
-  out = fp_to_mont(t);
-  return true;
-}
-
-ZK_DEV Fq fq_small(uint32_t x) {  // Montgomery form of a small constant
-  Fq t = fp_zero<FqP>();
-  t.v[0] = x;
-  return fp_to_mont(t);
-}
-
-// affine G1 from 16 std u32; status bits
-ZK_DEV uint32_t g1_load(const uint32_t* s, G1Aff& p) {
-  bool ok = fq_load_std(s, p.x) && fq_load_std(s + 8, p.y);
-  if (!ok) return ST_BAD;
-  if (aff_is_inf(p)) return ST_INF;
-  // y^2 == x^3 + 3
-  Fq lhs = fp_sqr(p.y);
-  Fq rhs = fp_add(fp_mul(fp_sqr(p.x), p.x), fq_small(3));
-  return fp_eq(lhs, rhs) ? 0u : ST_BAD;
-}
-
-ZK_DEV uint32_t g2_load(const uint32_t* s, G2Aff& q) {
-  bool ok = fq_load_std(s, q.x.c0) && fq_load_std(s + 8, q.x.c1) && fq_load_std(s + 16, q.y.c0) &&
-            fq_load_std(s + 24, q.y.c1);
-  if (!ok) return ST_BAD;
-  if (aff_is_inf(q)) return ST_INF;
-  Fq2 lhs = f2_sqr(q.y);
-  Fq2 rhs = f2_add(f2_mul(f2_sqr(q.x), q.x), load_fq2(TWIST_B));
-  return f2_eq(lhs, rhs) ? 0u : ST_BAD;
-}
-
-// psi (untwist-Frobenius-twist) on XYZZ coordinates: conj is a field automorphism, so
-// psi(X, Y, ZZ, ZZZ) = (conj(X) gx, conj(Y) gy, conj(ZZ), conj(ZZZ))
-ZK_DEV G2P g2_psi(const G2P& p) {
-  G2P r;
-  r.X = f2_mul(f2_conj(p.X), load_fq2(TWIST_FROB_X));
-  r.Y = f2_mul(f2_conj(p.Y), load_fq2(TWIST_FROB_Y));
-  r.ZZ = f2_conj(p.ZZ);
-  r.ZZZ = f2_conj(p.ZZZ);
-  return r;
-}
-
-ZK_DEV bool g2_eq(const G2P& a, const G2P& b) {
-  const bool ia = xyzz_is_inf(a), ib = xyzz_is_inf(b);
-  if (ia || ib) return ia && ib;
-  return f2_eq(f2_mul(a.X, b.ZZ), f2_mul(b.X, a.ZZ)) && f2_eq(f2_mul(a.Y, b.ZZZ), f2_mul(b.Y, a.ZZZ));
-}
 
 // Order-r subgroup membership of a twist point (G2 has a large cofactor), by the BN endomorphism
 // criterion [x0+1]P + psi([x0]P) + psi^2([x0]P) == psi^3([2 x0]P), x0 = u (ePrint 2022/348 §5.1):
@@ -98,10 +37,7 @@ ZK_DEV bool g2_in_subgroup(const G2Aff& q) {
   const uint32_t u[8] = {(uint32_t)BN_U, (uint32_t)(BN_U >> 32), 0, 0, 0, 0, 0, 0};
   const G2P p = xyzz_from_affine<Fq2Ops>(q);
   const G2P xp = xyzz_scalar_mul<Fq2Ops>(p, u);
-  const G2P pxp = g2_psi(xp);
-  G2P lhs = xyzz_add<Fq2Ops>(xyzz_add<Fq2Ops>(xyzz_add<Fq2Ops>(xp, p), pxp), g2_psi(pxp));
-  G2P rhs = g2_psi(g2_psi(g2_psi(xyzz_dbl<Fq2Ops>(xp))));
-  return g2_eq(lhs, rhs);
+  return g2_subgroup_criterion(p, xp);
 }
 
 __global__ __launch_bounds__(64) void k_g2_prepare(size_t n, const uint32_t* q_std, size_t q_stride, int subgroup,
@@ -253,15 +189,6 @@ hipError_t dalloc(T** p, size_t count) {
 }
 
 }  // namespace
-
-struct VkDev {
-  std::vector<uint8_t> bytes;
-  uint32_t npub = 0;
-  G1Aff* ic_table = nullptr;  // (npub+1) x 16; index 1 of row 0 = IC0
-  LineCoef* lines = nullptr;  // [3][ATE_NLINES]: beta2, gamma2, delta2
-  Fq12* f_ab = nullptr;       // Miller value of (alpha1, beta2), Montgomery
-  G1Aff* alpha = nullptr;
-};
 
 void vk_free(VkDev* vk) {
   if (!vk) return;

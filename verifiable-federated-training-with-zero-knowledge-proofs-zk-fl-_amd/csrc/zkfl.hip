@@ -548,6 +548,128 @@ int zkfl_debug_miller_loop(zkfl_ctx* ctx, size_t n, const uint8_t* g1, const uin
   return pairing_common(ctx, n, g1, g2, out, 0);
 }
 
+int zkfl_debug_wave_pairing(zkfl_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2, int final_exp,
+                            uint8_t* out) {
+  if (!ctx || (n && (!g1 || !g2 || !out))) return fail(ZKFL_E_ARG, "pairing: bad args");
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  std::string err;
+  int rc = pairing_wave_batch(n, g1, g2, final_exp, out, ctx->st, &ctx->prof, err);
+  return rc == ZKFL_OK ? rc : fail(rc, err);
+}
+
+// Resident verification keys; a round's proofs, each against its own key
+int zkfl_vkey_load(zkfl_ctx* ctx, const uint8_t* vk, size_t vk_len, zkfl_vkey** out) {
+  if (!ctx || !vk || !out) return fail(ZKFL_E_ARG, "vkey_load: null argument");
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  std::string err;
+  VkDev* p = nullptr;
+  int rc = vk_prepare(vk, vk_len, ctx->st, &p, err);
+  if (rc != ZKFL_OK) return fail(rc, err);
+  void* wtab = nullptr;
+  rc = vk_wave_tables(p, ctx->st, &wtab, err);
+  if (rc != ZKFL_OK) {
+    vk_free(p);
+    return fail(rc, err);
+  }
+  zkfl_vkey* k = new zkfl_vkey();
+  k->ctx = ctx;
+  k->vk = p;
+  k->wtab = wtab;
+  k->wave_ok = vk_npub(p) <= ZKFL_VERIFY_WAVE_MAX_PUBLIC;
+  ctx_retain(ctx);
+  *out = k;
+  return ZKFL_OK;
+}
+
+int zkfl_vkey_info(const zkfl_vkey* key, uint32_t* n_public) {
+  if (!key) return fail(ZKFL_E_ARG, "vkey_info: null key");
+  if (n_public) *n_public = vk_npub(key->vk);
+  return ZKFL_OK;
+}
+
+int zkfl_vkey_free(zkfl_vkey* key) {
+  if (!key) return fail(ZKFL_E_ARG, "vkey_free: null key");
+  zkfl_ctx* ctx = key->ctx;
+  (void)hipSetDevice(ctx->device);
+  (void)hipStreamSynchronize(ctx->st);
+  vk_wave_tables_free(key->wtab);
+  vk_free(key->vk);
+  delete key;
+  ctx_release(ctx);
+  return ZKFL_OK;
+}
+
+int zkfl_groth16_verify_multi(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
+                              const size_t* npubs, const uint8_t* proofs, int32_t* results, int schedule) {
+  if (!ctx || (n && (!vkeys || !pubs || !npubs || !proofs || !results)))
+    return fail(ZKFL_E_ARG, "verify_multi: null argument");
+  if (schedule != ZKFL_VERIFY_AUTO && schedule != ZKFL_VERIFY_LANES && schedule != ZKFL_VERIFY_WAVES)
+    return fail(ZKFL_E_ARG, "verify_multi: unknown schedule " + std::to_string(schedule));
+  for (size_t i = 0; i < n; i++) {
+    if (!vkeys[i] || vkeys[i]->ctx != ctx)
+      return fail(ZKFL_E_ARG, "verify_multi: job " + std::to_string(i) + " has no key of this context");
+    const uint32_t want = vk_npub(vkeys[i]->vk);
+    if (npubs[i] != want)
+      return fail(ZKFL_E_MISMATCH, "verify_multi: job " + std::to_string(i) + " has " + std::to_string(npubs[i]) +
+                                       " public signals, its key expects " + std::to_string(want));
+    if (want && !pubs[i]) return fail(ZKFL_E_ARG, "verify_multi: job " + std::to_string(i) + " has null publics");
+  }
+  if (n == 0) return ZKFL_OK;
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  if (schedule == ZKFL_VERIFY_AUTO)
+    schedule = n <= ZKFL_VERIFY_AUTO_WAVES_MAX ? ZKFL_VERIFY_WAVES : ZKFL_VERIFY_LANES;
+  // the wave jobs, in job order; every other job by key, in order of first appearance
+  std::vector<size_t> wave;
+  std::vector<const zkfl_vkey*> lane_keys;
+  std::vector<std::vector<size_t>> lane_jobs;
+  for (size_t i = 0; i < n; i++) {
+    if (schedule == ZKFL_VERIFY_WAVES && vkeys[i]->wave_ok) {
+      wave.push_back(i);
+      continue;
+    }
+    size_t g = 0;
+    while (g < lane_keys.size() && lane_keys[g] != vkeys[i]) g++;
+    if (g == lane_keys.size()) {
+      lane_keys.push_back(vkeys[i]);
+      lane_jobs.emplace_back();
+    }
+    lane_jobs[g].push_back(i);
+  }
+  std::vector<int32_t> res(n, 0), part;
+  std::vector<uint8_t> pr, pb;
+  std::string err;
+  int rc = ZKFL_OK;
+  if (!wave.empty()) {
+    std::vector<VerifyJob> jobs(wave.size());
+    pr.resize(256 * wave.size());
+    part.assign(wave.size(), 0);
+    for (size_t j = 0; j < wave.size(); j++) {
+      const size_t i = wave[j];
+      jobs[j] = {vkeys[i]->vk, vkeys[i]->wtab, pubs[i]};
+      memcpy(pr.data() + 256 * j, proofs + 256 * i, 256);
+    }
+    rc = verify_wave(wave.size(), jobs.data(), pr.data(), part.data(), ctx->st, &ctx->prof, err);
+    if (rc != ZKFL_OK) return fail(rc, err);
+    for (size_t j = 0; j < wave.size(); j++) res[wave[j]] = part[j];
+  }
+  for (size_t g = 0; g < lane_keys.size(); g++) {
+    const std::vector<size_t>& idx = lane_jobs[g];
+    const size_t np = vk_npub(lane_keys[g]->vk);
+    pr.resize(256 * idx.size());
+    pb.resize(32 * np * idx.size() + 1);
+    part.assign(idx.size(), 0);
+    for (size_t j = 0; j < idx.size(); j++) {
+      memcpy(pr.data() + 256 * j, proofs + 256 * idx[j], 256);
+      if (np) memcpy(pb.data() + 32 * np * j, pubs[idx[j]], 32 * np);
+    }
+    rc = verify_batch(lane_keys[g]->vk, idx.size(), pb.data(), pr.data(), part.data(), ctx->st, err);
+    if (rc != ZKFL_OK) return fail(rc, err);
+    for (size_t j = 0; j < idx.size(); j++) res[idx[j]] = part[j];
+  }
+  memcpy(results, res.data(), n * sizeof(int32_t));
+  return ZKFL_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Witness generation (csrc/witness.hip)
 // ---------------------------------------------------------------------------

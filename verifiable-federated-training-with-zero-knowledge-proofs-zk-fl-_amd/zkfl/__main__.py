@@ -20,11 +20,16 @@
     python -m zkfl prove <zkey> <wtns> <proof.json> <public.json> [--r1cs <circuit.r1cs>]   snarkjs groth16 prove
         (:773-776); --r1cs: check the witness first, exit 1 without writing a proof when it fails
     python -m zkfl verify <vkey.json> <public.json> <proof.json>            snarkjs groth16 verify (:865-868)
+    python -m zkfl verify-round <round.json>                 a round's `groth16 verify` calls (:1298-1343) as one
+        verify_multi call.  round.json: a list of {"vkey": path, "public": path, "proof": path} (relative
+        paths are taken from the manifest's directory); each distinct vkey is loaded once.  Prints one
+        line per job, in job order; exit 0 if all are valid, 1 if any is invalid, 2 on a manifest that
+        is not such a list or names a missing file (decided before the GPU is touched)
 
 <circuit> is one of zkfl.circuits.CIRCUITS (poseidon_hash2, sgd_verified, sgd_step_v5,
 balance_unified, secure_masked_update) followed by its integer template parameters.  GPU
-commands use device $LOCAL_RANK (default 0).  Exit status 0 on success; verify exits 1 on an
-invalid proof, like snarkjs.
+commands use device $LOCAL_RANK (default 0).  Exit status 0 on success; verify and verify-round
+exit 1 on an invalid proof, like snarkjs.
 """
 
 from __future__ import annotations
@@ -160,6 +165,52 @@ def cmd_verify(args):
     return 1
 
 
+def _round_manifest(path):
+    """round.json -> [(vkey path, public path, proof path)], or None with a message on stderr."""
+    try:
+        with open(path) as f:
+            man = json.load(f)
+    except (OSError, ValueError) as e:
+        print(f"[ERROR] zkfl: {path}: {e}", file=sys.stderr)
+        return None
+    keys = ("vkey", "public", "proof")
+    if not isinstance(man, list) or not all(
+            isinstance(j, dict) and all(isinstance(j.get(k), str) for k in keys) for j in man):
+        print(f"[ERROR] zkfl: {path}: expected a list of {{\"vkey\", \"public\", \"proof\"}} paths", file=sys.stderr)
+        return None
+    base = os.path.dirname(os.path.abspath(path))
+    jobs = [tuple(os.path.join(base, j[k]) for k in keys) for j in man]
+    for job in jobs:
+        for f in job:
+            if not os.path.isfile(f):
+                print(f"[ERROR] zkfl: {path}: no such file: {f}", file=sys.stderr)
+                return None
+    return jobs
+
+
+def cmd_verify_round(args):
+    jobs = _round_manifest(args.round)
+    if jobs is None:
+        return 2
+    try:
+        data = [tuple(json.load(open(f)) for f in job) for job in jobs]
+    except ValueError as e:
+        print(f"[ERROR] zkfl: {args.round}: {e}", file=sys.stderr)
+        return 2
+    p = groth16.Prover(int(os.environ.get("LOCAL_RANK", "0")))
+    try:
+        handles = {}
+        for (vpath, _, _), (vk, _, _) in zip(jobs, data):
+            if vpath not in handles:
+                handles[vpath] = p.load_vkey(vk)
+        oks = p.verify_multi([(handles[j[0]], d[1], d[2]) for j, d in zip(jobs, data)])
+    finally:
+        p.close()
+    for i, ok in enumerate(oks):
+        print(f"job {i}: " + ("[INFO]  snarkJS: OK!" if ok else "[ERROR] snarkJS: Invalid proof"))
+    return 0 if all(oks) else 1
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     if snarkjs_cli.routes(argv):   # snarkjs ceremony strings and `wtns check` (zkfl/snarkjs_cli.py)
@@ -200,10 +251,12 @@ def main(argv=None):
     sp = sub.add_parser("verify")
     for a in ("vkey", "public", "proof"):
         sp.add_argument(a)
+    sp = sub.add_parser("verify-round")
+    sp.add_argument("round")
     args = ap.parse_args(argv)
     fn = {"compile": cmd_compile, "info": cmd_info, "setup": cmd_setup,
           "r1cs-info": cmd_r1cs_info, "setup-r1cs": cmd_setup_r1cs, "export-vk": cmd_export_vk,
-          "wtns": cmd_wtns, "prove": cmd_prove, "verify": cmd_verify}[args.cmd]
+          "wtns": cmd_wtns, "prove": cmd_prove, "verify": cmd_verify, "verify-round": cmd_verify_round}[args.cmd]
     try:
         return fn(args) or 0
     except native.ZkflError as e:

@@ -133,6 +133,7 @@ class Prover:
     def __init__(self, device: int = 0):
         self.ctx = native.Context(device)
         self._keys = {}
+        self._vkeys = {}
         self._progs = {}
 
     def program(self, circuit) -> native.WitnessProgram:
@@ -178,10 +179,29 @@ class Prover:
         return self.ctx.verify_batch(vk_bytes(vk), b"".join(public_bytes(p) for p in publics),
                                      b"".join(proof_from_json(p) for p in proofs), int(vk["nPublic"]))
 
+    def load_vkey(self, vk: dict) -> native.VerifyingKey:
+        """vkey.json dict -> a device-resident verification key (loaded once per distinct key)."""
+        image = vk_bytes(vk)
+        digest = hashlib.sha256(image).digest()
+        k = self._vkeys.get(digest)
+        if k is None or not k.h:
+            k = native.VerifyingKey(self.ctx, image)
+            self._vkeys[digest] = k
+        return k
+
+    def verify_multi(self, jobs, schedule: str = "auto") -> list:
+        """jobs: [(vkey.json dict or load_vkey handle, publicSignals, proof.json dict)] -> [bool]:
+        a round's proofs, each against its own resident key, in one call (the server's loop,
+        tests/full_system_simulation.mjs:1298-1343)."""
+        return self.ctx.verify_multi(
+            [(vk if isinstance(vk, native.VerifyingKey) else self.load_vkey(vk), public_bytes(pub),
+              proof_from_json(proof)) for vk, pub, proof in jobs], schedule)
+
     def close(self):
-        for k in self._keys.values():
+        for k in list(self._keys.values()) + list(self._vkeys.values()):
             k.close()
         self._keys.clear()
+        self._vkeys.clear()
         for _, p in self._progs.values():
             p.close()
         self._progs.clear()
@@ -225,6 +245,16 @@ def verify(vk: dict, public, proof: dict) -> bool:
     return _prover().verify(vk, public, proof)
 
 
-__all__ = ["prove", "fullProve", "verify", "Prover", "proof_to_json", "proof_from_json", "export_verification_key",
+def load_vkey(vk: dict) -> native.VerifyingKey:
+    """A vkey.json dict made device-resident on the default prover (Prover.load_vkey)."""
+    return _prover().load_vkey(vk)
+
+
+def verify_multi(jobs, schedule: str = "auto") -> list:
+    """[(vKey or load_vkey handle, publicSignals, proof)] -> [bool] in one call (Prover.verify_multi)."""
+    return _prover().verify_multi(jobs, schedule)
+
+
+__all__ = ["prove", "fullProve", "verify", "verify_multi", "load_vkey", "Prover", "proof_to_json", "proof_from_json", "export_verification_key",
            "vk_bytes", "public_bytes", "wtns_calculate", "r1cs_info", "read_wtns", "wtns_check",
            "wtns_check_report"]

@@ -96,6 +96,12 @@ SIGNATURES = {
                                             C.c_char_p, C.POINTER(C.c_int32)]),
     "zkfl_pairing": (C.c_int, [_P, C.c_size_t, C.c_char_p, C.c_char_p, _U8P]),
     "zkfl_debug_miller_loop": (C.c_int, [_P, C.c_size_t, C.c_char_p, C.c_char_p, _U8P]),
+    "zkfl_vkey_load": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(_P)]),
+    "zkfl_vkey_info": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "zkfl_vkey_free": (C.c_int, [_P]),
+    "zkfl_groth16_verify_multi": (C.c_int, [_P, C.c_size_t, C.POINTER(_P), C.POINTER(C.c_char_p),
+                                            C.POINTER(C.c_size_t), C.c_char_p, C.POINTER(C.c_int32), C.c_int]),
+    "zkfl_debug_wave_pairing": (C.c_int, [_P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_int, _U8P]),
     "zkfl_wprog_load": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(_P)]),
     "zkfl_wprog_free": (C.c_int, [_P]),
     "zkfl_wprog_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -393,6 +399,33 @@ class Context:
         check(lib().zkfl_groth16_verify_batch(self.h, vk, len(vk), n, publics, npub, proofs, res))
         return [bool(res[i]) for i in range(n)]
 
+    def verify_multi(self, jobs, schedule: str = "auto") -> list:
+        """jobs: [(VerifyingKey, public bytes, proof bytes)], each proof against its own resident
+        key, in one call -> [bool] in job order.  schedule: "auto", "lanes" (one proof per lane,
+        grouped by key) or "waves" (one proof per wavefront: the latency of a round)."""
+        sched = VERIFY_SCHEDULES.get(schedule, schedule)
+        if not isinstance(sched, int):
+            raise ValueError(f"schedule must be one of {sorted(VERIFY_SCHEDULES)}")
+        n = len(jobs)
+        for _, public, proof in jobs:
+            assert len(proof) == 256 and len(public) % 32 == 0
+        keys = (_P * max(1, n))(*[k.h for k, _, _ in jobs])
+        pubs = (C.c_char_p * max(1, n))(*[bytes(p) for _, p, _ in jobs])
+        npubs = (C.c_size_t * max(1, n))(*[len(p) // 32 for _, p, _ in jobs])
+        res = (C.c_int32 * max(1, n))()
+        check(lib().zkfl_groth16_verify_multi(self.h, n, keys, pubs, npubs, b"".join(pr for _, _, pr in jobs),
+                                              res, sched))
+        return [bool(res[i]) for i in range(n)]
+
+    def wave_pairing(self, g1: bytes, g2: bytes, final_exp: bool = True) -> bytes:
+        """pairing() computed by the wave verifier's tower, Miller loop and final exponentiation
+        (one pair per wavefront): the parity hook of Context.verify_multi's "waves" schedule."""
+        n = len(g1) // 64
+        assert len(g1) == 64 * n and len(g2) == 128 * n
+        out = _buf(384 * n if n else 1)
+        check(lib().zkfl_debug_wave_pairing(self.h, n, g1, g2, 1 if final_exp else 0, out))
+        return bytes(out)[:384 * n]
+
     # Poseidon / vectorHash / Merkle trees (the reference's data and server side)
     def poseidon_batch(self, rows) -> list:
         """[[ints] * arity] -> [Poseidon(row)] (circomlibjs poseidon, on the GPU)."""
@@ -486,6 +519,35 @@ class Context:
         fn = lib().zkfl_pairing if final_exp else lib().zkfl_debug_miller_loop
         check(fn(self.h, n, g1, g2, out))
         return bytes(out)[:384 * n]
+
+
+VERIFY_SCHEDULES = {"auto": 0, "lanes": 1, "waves": 2}  # ZKFL_VERIFY_*
+
+
+class VerifyingKey:
+    """A verification key made device-resident (zkfl_vkey_load): vk_bytes is the vk image of
+    Context.verify (zkfl.groth16.vk_bytes).  Any number may be resident on a context."""
+
+    def __init__(self, ctx: Context, vk_bytes: bytes):
+        h = _P()
+        check(lib().zkfl_vkey_load(ctx.h, vk_bytes, len(vk_bytes), C.byref(h)))
+        self.h = h
+        self.ctx = ctx
+        ctx._own(self)
+        npub = C.c_uint32()
+        check(lib().zkfl_vkey_info(h, C.byref(npub)))
+        self.n_public = npub.value
+
+    def close(self):
+        if self.h:
+            lib().zkfl_vkey_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ProvingKey:
