@@ -49,6 +49,7 @@ extern "C" {
 #define ZKFL_E_DEVICE -5     /* HIP runtime error / no GPU */
 #define ZKFL_E_OOM -6        /* device allocation failed */
 #define ZKFL_E_CONSTRAINT -7 /* witness does not satisfy the circuit */
+#define ZKFL_E_KEY -8        /* proving key is not the circuit's key over the ptau (zkfl_zkey_check) */
 
 typedef struct zkfl_ctx zkfl_ctx;
 typedef struct zkfl_key zkfl_key;
@@ -72,7 +73,8 @@ int zkfl_ctx_destroy(zkfl_ctx* ctx);
 int zkfl_ctx_set_profiling(zkfl_ctx* ctx, int enabled);
 /* name: "msm_accumulate_g1", "msm_accumulate_g2", "ntt", "abc", "prove", "witness" (full-prove
  * slots), "r1cs_terms", "r1cs_verdict" (the witness check's two passes), "verify_wave_g2",
- * "verify_wave_inputs", "verify_wave_pair" (the wave verifier's three kernels; units: proofs).
+ * "verify_wave_inputs", "verify_wave_pair" (the wave verifier's three kernels; units: proofs),
+ * "keycheck_points", "keycheck_rows", "keycheck_msm", "keycheck_pairing" (the key check's stages).
  * Synchronises the device.
  * total_ms: summed event time; units: summed algorithmic units (MSM entries, NTT elements...);
  * median_ms (nullable): median single-launch time, robust to a one-off stalled dispatch. */
@@ -295,6 +297,73 @@ int zkfl_r1cs_check(zkfl_ctx* ctx, const zkfl_r1cs* r1cs, size_t n, const uint8_
                     zkfl_r1cs_report* reports);
 int zkfl_r1cs_check_resident(zkfl_ctx* ctx, const zkfl_r1cs* r1cs, size_t n, const zkfl_witness* const* w,
                              zkfl_r1cs_report* reports);
+
+/* Key check: is this .zkey the Groth16 proving key of this .r1cs over this prepared .ptau, for some
+ * delta (and gamma)?  The reference proves with whatever `<c>_final.zkey` lies in the circuit
+ * directory and skips `groth16 setup` + `zkey contribute` when one is there
+ * (tests/full_system_simulation.mjs:713-738), and zkfl_zkey_load validates a key's layout, not its
+ * content: a wrong key otherwise shows only as an invalid proof.  No snarkjs command asks this
+ * (`zkey verify` asserts a contribution transcript, which this call does not read).
+ *
+ * With rho (n_wires scalars) and sigma (domainSize scalars) uniform below r, a(rho), b(rho), c(rho) the
+ * .r1cs rows evaluated on rho (plus the public rows a[m + s] += rho[s], s <= nPublic) and
+ * K(v) = MSM(Lb, a(v)) + MSM(La, b(v)) + MSM(L, c(v)), the checks are, in this order:
+ *   HEADER        alpha1, beta1, beta2 are the ptau's; gamma2, delta1, delta2 are proper points;
+ *                 e(delta1, G2) == e(G1, delta2)
+ *   POINTS        every point of the header and of sections 3, 5, 6, 7, 8, 9 is all-zero (infinity)
+ *                 or has coordinates < q and lies on its curve; G2 points lie in the order-r subgroup
+ *   COEFFICIENTS  section 4 evaluated on rho equals a(rho), b(rho) row for row (zero elsewhere)
+ *   A, B1, B2     MSM(section 5 | 6 | 7, rho) == MSM(L, a(rho)) | MSM(L, b(rho)) | MSM(L2, b(rho))
+ *   IC            e(MSM(section 3, rho[0..nPublic]), gamma2) == e(K(rho on the public wires), G2)
+ *   C             e(MSM(section 8, rho[nPublic+1..]), delta2) == e(K(rho on the other wires), G2)
+ *   H             e(MSM(section 9, sigma), delta2) == e(MSM(H0, sigma), G2)
+ * A false accept needs a non-zero linear form to vanish at a uniform point: probability <= 2^-253
+ * per check.  A section with a bad point (and IC / C / H under an unusable gamma2 / delta2) takes no
+ * part in the later checks, which then read ZKFL_KEYCHECK_NOT_RUN.
+ *
+ * zkfl_ptau_view: the ptau's Lagrange blocks at the circuit's power (domainSize = 2^power points
+ * each, mont affine as the file stores them): L = section 12, L2 = section 13 (G2), La = section
+ * 14, Lb = section 15, H0[j] = point 2 j + 1 of section 12's block at power + 1; alpha1 / beta1 /
+ * beta2 = alphaTauG1[0], betaTauG1[0], betaG2 (64, 64, 128 B).  *_len are byte lengths.
+ *
+ * zkfl_zkey_report: status[] per check; point_* = the first section (2 = header, points numbered
+ * alpha1, beta1, beta2, gamma2, delta1, delta2) with a bad point, its lowest bad index and how many
+ * of its points are bad; coef_* = matrix and row of the lowest differing row and the number of
+ * differing rows.
+ *
+ * rho / sigma NULL: drawn from the OS CSPRNG (as rs == NULL for proofs).  Non-NULL values are for
+ * tests and forfeit soundness: a key can be made to pass a vector known in advance.
+ * Returns ZKFL_OK when every check holds; ZKFL_E_KEY when one does not (zkfl_last_error names the
+ * first in the order above and, for points, section and index; the report is filled);
+ * ZKFL_E_MISMATCH when nVars / nPublic / domainSize disagree with the r1cs or the view's power,
+ * ZKFL_E_ARG for a short block, a scalar >= r or an r1cs of another context, the parser's codes for
+ * a malformed key -- all before any device work. */
+#define ZKFL_KEYCHECK_HEADER 0
+#define ZKFL_KEYCHECK_POINTS 1
+#define ZKFL_KEYCHECK_COEFFICIENTS 2
+#define ZKFL_KEYCHECK_A 3
+#define ZKFL_KEYCHECK_B1 4
+#define ZKFL_KEYCHECK_B2 5
+#define ZKFL_KEYCHECK_IC 6
+#define ZKFL_KEYCHECK_C 7
+#define ZKFL_KEYCHECK_H 8
+#define ZKFL_KEYCHECK_N 9
+#define ZKFL_KEYCHECK_PASS 0
+#define ZKFL_KEYCHECK_FAIL 1
+#define ZKFL_KEYCHECK_NOT_RUN 2
+typedef struct {
+  uint32_t power;
+  const uint8_t *L, *L2, *La, *Lb, *H0;
+  size_t L_len, L2_len, La_len, Lb_len, H0_len;
+  const uint8_t *alpha1, *beta1, *beta2;
+} zkfl_ptau_view;
+typedef struct {
+  uint32_t status[ZKFL_KEYCHECK_N];
+  uint32_t point_section, point_index, point_count;
+  uint32_t coef_matrix, coef_row, coef_count;
+} zkfl_zkey_report;
+int zkfl_zkey_check(zkfl_ctx* ctx, const zkfl_r1cs* r1cs, const uint8_t* zkey, size_t zkey_len,
+                    const zkfl_ptau_view* ptau, const uint8_t* rho, const uint8_t* sigma, zkfl_zkey_report* report);
 
 /* Verification (replaces `snarkjs groth16 verify <vkey> <public> <proof>`,
  * tests/full_system_simulation.mjs:865-868; snarkjs groth16_verify, restated in

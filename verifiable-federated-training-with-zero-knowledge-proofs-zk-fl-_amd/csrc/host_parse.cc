@@ -503,6 +503,7 @@ int zkey_parse(const uint8_t* buf, size_t len, ZkeyHost& z, std::string& err) {
       s[6].size != (size_t)z.nVars * 64 || s[7].size != (size_t)z.nVars * 128 || s[8].size != z.nC * 64 ||
       s[9].size != (size_t)z.dom * 64)
     return bad(err, ZKFL_E_MISMATCH, "zkey: section sizes do not match header");
+  z.secIC = buf + s[3].off;
   z.secA = buf + s[5].off;
   z.secB1 = buf + s[6].off;
   z.secB2 = buf + s[7].off;

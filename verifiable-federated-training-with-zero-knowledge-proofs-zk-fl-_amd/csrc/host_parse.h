@@ -41,7 +41,7 @@ struct ZkeyHost {
   int logn = 0;
   size_t nC = 0;  // C query length nVars - nPub - 1
   const uint8_t* pts = nullptr;  // alpha1 64 | beta1 64 | beta2 128 | gamma2 128 | delta1 64 | delta2 128
-  const uint8_t *secA = nullptr, *secB1 = nullptr, *secB2 = nullptr, *secC = nullptr, *secH = nullptr;
+  const uint8_t *secIC = nullptr, *secA = nullptr, *secB1 = nullptr, *secB2 = nullptr, *secC = nullptr, *secH = nullptr;
   size_t ncoef = 0;
   std::vector<uint32_t> rowptr;  // [2 (dom + 1)]: A row pointers, then B row pointers offset by nnz(A)
   std::vector<uint32_t> cols;    // packed terms (col | dict index << cshift) or plain columns

@@ -27,6 +27,18 @@ struct R1csVerdict {
 
 }  // namespace zkfl
 
+struct zkfl_r1cs;
+
+namespace zkfl {
+
+// The terms pass alone, on the context's stream: k_abc_chunks over the object's 3 m rows with the
+// vector w (device, std form, n_wires long), leaving head / tail / abc for abc_row.  The witness
+// check runs it per witness; the key check (csrc/keycheck.hip) runs it on its random vectors.
+// Launches nothing when the system has no terms (every row is then zero).
+void r1cs_terms(hipStream_t st, const zkfl_r1cs* r, const Fr* w);
+
+}  // namespace zkfl
+
 struct zkfl_r1cs {
   zkfl_ctx* ctx = nullptr;
   zkfl_r1cs_header hdr = {};

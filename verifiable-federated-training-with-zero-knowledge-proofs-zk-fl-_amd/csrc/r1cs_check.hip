@@ -122,7 +122,6 @@ int run_checks(zkfl_ctx* ctx, const zkfl_r1cs* r, size_t n, const Fr* const* d_w
     HIP_TRY(hipMalloc(&r->verdicts, n * sizeof(R1csVerdict)), "alloc verdicts");
     r->verdict_cap = n;
   }
-  const AbcTerms T = {r->cols, r->coefs, r->cshift};
   const uint32_t m = r->m, K = r->K;
   for (size_t i = 0; i < n; i++) {
     const Fr* w = d_w ? d_w[i] : r->w;
@@ -134,7 +133,7 @@ int run_checks(zkfl_ctx* ctx, const zkfl_r1cs* r, size_t n, const Fr* const* d_w
       continue;
     }
     int pi = ctx->prof.begin("r1cs_terms", st);
-    if (K) abc_chunks(st, r->rows, 3 * m, T, w, K, r->head, r->tail, r->abc);  // no terms: every row is zero
+    r1cs_terms(st, r, w);
     ctx->prof.end(pi, st, (double)K);
     pi = ctx->prof.begin("r1cs_verdict", st);
     hipLaunchKernelGGL(k_r1cs_verdict, dim3(zk_grid(m, 256)), dim3(256), 0, st, r->rows, m, K, r->head, r->tail,
@@ -166,6 +165,11 @@ int run_checks(zkfl_ctx* ctx, const zkfl_r1cs* r, size_t n, const Fr* const* d_w
 }
 
 }  // namespace
+
+void zkfl::r1cs_terms(hipStream_t st, const zkfl_r1cs* r, const Fr* w) {
+  const AbcTerms T = {r->cols, r->coefs, r->cshift};
+  if (r->K && r->m) abc_chunks(st, r->rows, 3 * r->m, T, w, r->K, r->head, r->tail, r->abc);  // no terms: every row is zero
+}
 
 extern "C" {
 

@@ -265,10 +265,24 @@ function wtnsCheck(r1csFile, wtnsFile) {
   });
 }
 
+// zKey.check(r1csFileName, ptauFileName, zkeyFileName) -> true / false: is the key the circuit's
+// Groth16 key over that prepared ptau, for some delta?  The Python host's `zkey check` (libzkfl
+// zkfl_zkey_check) as a child process, its report on this process's stderr.  Not a snarkjs call:
+// snarkjs's zKey.verify asserts a contribution transcript, which this does not test.
+function zkeyCheck(r1csFile, ptauFile, zkeyFile) {
+  return new Promise((resolve, reject) => {
+    const c = require('child_process').spawn(process.env.ZKFL_PYTHON || 'python3',
+      ['-m', 'zkfl', 'zkey', 'check', r1csFile, ptauFile, zkeyFile], { stdio: ['ignore', 'ignore', 'inherit'], env: hostEnv() });
+    c.on('error', reject);
+    c.on('exit', (code) => (code === 0 || code === 1 ? resolve(code === 0)
+      : reject(new Error('zkey check: the zkfl host exited with status ' + code))));
+  });
+}
+
 module.exports = {
   groth16: { prove, fullProve, verify },
   wtns: { calculate: wtnsCalculate, check: wtnsCheck },
-  zKey: { exportVerificationKey },
+  zKey: { exportVerificationKey, check: zkeyCheck },
   r1cs: { info: r1csInfo },
   addon, proofToJson, vkBuffer,
 };
@@ -295,12 +309,14 @@ function done(p) {
 // the same libzkfl (zkfl_setup_*: scalar multiplications, group FFTs and sparse combinations on the
 // GPU): `python3 -m zkfl <the same argv>` as a child process, its exit status passed through.
 // `wtns check <c.r1cs> <w.wtns>` (alias wchk) goes the same way: the addon has no binding of its own.
+// So does `zkey check <c.r1cs> <pot.ptau> <c.zkey>` (libzkfl zkfl_zkey_check; not a snarkjs command:
+// `zkey verify` asserts a contribution transcript and stays unserved).
 const CEREMONY = new Set(['powersoftau', 'ptn', 'ptc', 'pt2', 'g16s', 'zkn', 'zkc', 'wchk']);
 
 function isCeremony(argv) {
   const a = argv.filter((x) => !x.startsWith('-'));
   return CEREMONY.has(a[0]) || (a[0] === 'groth16' && a[1] === 'setup') || (a[0] === 'wtns' && a[1] === 'check') ||
-    (a[0] === 'zkey' && (a[1] === 'new' || a[1] === 'contribute'));
+    (a[0] === 'zkey' && (a[1] === 'new' || a[1] === 'contribute' || a[1] === 'check'));
 }
 
 function hostEnv() {
@@ -373,7 +389,8 @@ if (require.main === module && isCeremony(process.argv.slice(2))) {
                   '       snarkjs powersoftau contribute <in.ptau> <out.ptau> [-e=entropy] [--name=name]\n' +
                   '       snarkjs powersoftau prepare phase2 <in.ptau> <out.ptau>\n' +
                   '       snarkjs groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>\n' +
-                  '       snarkjs zkey contribute <in.zkey> <out.zkey> [--name=name] [-e=entropy]');
+                  '       snarkjs zkey contribute <in.zkey> <out.zkey> [--name=name] [-e=entropy]\n' +
+                  '       snarkjs zkey check <circuit.r1cs> <pot_final.ptau> <circuit.zkey>');
     process.exit(99);
   }
 }

@@ -18,7 +18,11 @@
     python -m zkfl wtns check <circuit.r1cs> <witness.wtns>                 snarkjs wtns check (alias: wchk); exit 1
                                                                             and the first failing constraint otherwise
     python -m zkfl prove <zkey> <wtns> <proof.json> <public.json> [--r1cs <circuit.r1cs>]   snarkjs groth16 prove
-        (:773-776); --r1cs: check the witness first, exit 1 without writing a proof when it fails
+        (:773-776); --r1cs: check the witness first, exit 1 without writing a proof when it fails;
+        --check-key <circuit.r1cs> <pot_final.ptau>: check the key first (as `zkey check`), the same way
+    python -m zkfl zkey check <circuit.r1cs> <pot_final.ptau> <circuit.zkey>   is the key the circuit's Groth16 key over
+        that prepared ptau, for some delta?  One line per check; exit 0, 1 when a check fails, 2 on
+        unusable arguments (the reference trusts any `<c>_final.zkey` it finds, :713-738)
     python -m zkfl verify <vkey.json> <public.json> <proof.json>            snarkjs groth16 verify (:865-868)
     python -m zkfl verify-round <round.json>                 a round's `groth16 verify` calls (:1298-1343) as one
         verify_multi call.  round.json: a list of {"vkey": path, "public": path, "proof": path} (relative
@@ -145,7 +149,7 @@ def cmd_wtns(args):
 def cmd_prove(args):
     p = groth16.Prover(int(os.environ.get("LOCAL_RANK", "0")))
     try:
-        proof, public = p.prove(args.zkey, args.wtns, r1cs=args.r1cs)
+        proof, public = p.prove(args.zkey, args.wtns, r1cs=args.r1cs, check_key=args.check_key)
     finally:
         p.close()
     with open(args.proof, "w") as f:
@@ -248,6 +252,8 @@ def main(argv=None):
     for a in ("zkey", "wtns", "proof", "public"):
         sp.add_argument(a)
     sp.add_argument("--r1cs", default=None, help="check the witness against this .r1cs before proving")
+    sp.add_argument("--check-key", nargs=2, default=None, metavar=("R1CS", "PTAU"),
+                    help="check the key against this .r1cs and prepared .ptau before loading it")
     sp = sub.add_parser("verify")
     for a in ("vkey", "public", "proof"):
         sp.add_argument(a)

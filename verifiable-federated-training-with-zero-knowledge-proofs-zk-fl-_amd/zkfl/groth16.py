@@ -8,6 +8,7 @@ Mirrors the snarkjs API/CLI the reference harness drives:
   ``r1cs_info(circuit)``                   <- ``snarkjs r1cs info`` (tests/test_verified_gradient.mjs:351-356)
   ``verify(vkey, public, proof)``          <- ``snarkjs groth16 verify`` (:865-868), on the GPU
   ``wtns_check(r1cs, wtns)``               <- ``snarkjs wtns check <c.r1cs> <w.wtns>`` (snarkjs ``wtns.check``), on the GPU
+  ``zkey_check(r1cs, ptau, zkey)``         the key against its circuit and ptau (no snarkjs counterpart), on the GPU
 Outputs are snarkjs's JSON shapes: proof.json = {pi_a, pi_b, pi_c, protocol, curve} with
 decimal strings, public.json = list of decimal strings (witness[1..nPublic]).
 """
@@ -156,11 +157,18 @@ class Prover:
             self._keys[digest] = k
         return k
 
-    def prove(self, zkey, wtns, rs: bytes | None = None, r1cs=None):
+    def prove(self, zkey, wtns, rs: bytes | None = None, r1cs=None, check_key=None):
         """-> (proof.json dict, public.json list).  r1cs (bytes or path): the witness is checked
         against it first, and one that does not satisfy it raises ZkflError(ZKFL_E_CONSTRAINT)
-        instead of yielding a proof that cannot verify."""
+        instead of yielding a proof that cannot verify.  check_key = (r1cs, ptau): the key is
+        checked against them before it is loaded (zkfl/keycheck.py); one that fails raises
+        ZkflError(ZKFL_E_KEY)."""
         wtns = _read(wtns)
+        if check_key is not None:
+            from . import keycheck
+            rep = keycheck.zkey_check(check_key[0], check_key[1], zkey, self.ctx)
+            if not rep.ok:
+                raise native.ZkflError(-8, rep.error)
         if r1cs is not None:
             with native.R1cs(self.ctx, _read(r1cs)) as cs:
                 if not cs.check([wtns], reports=False):
@@ -218,8 +226,8 @@ def _prover() -> Prover:
     return _default
 
 
-def prove(zkey, wtns, rs: bytes | None = None, r1cs=None):
-    return _prover().prove(zkey, wtns, rs, r1cs=r1cs)
+def prove(zkey, wtns, rs: bytes | None = None, r1cs=None, check_key=None):
+    return _prover().prove(zkey, wtns, rs, r1cs=r1cs, check_key=check_key)
 
 
 def wtns_check_report(r1cs, wtns, ctx: native.Context | None = None) -> native.Report:
@@ -234,6 +242,14 @@ def wtns_check(r1cs, wtns, ctx: native.Context | None = None) -> bool:
     holds for the witness (checked on the GPU).  A malformed file, or a witness of another length
     than the circuit's wires, raises ZkflError."""
     return wtns_check_report(r1cs, wtns, ctx).ok
+
+
+def zkey_check(r1cs, ptau, zkey, ctx: native.Context | None = None) -> native.KeyReport:
+    """Is ``zkey`` the Groth16 proving key of ``r1cs`` over the prepared ``ptau`` (bytes or paths),
+    for some delta and gamma?  -> the report (``.ok``, ``.checks``, ``.error``), checked on the GPU
+    (zkfl/keycheck.py).  No snarkjs counterpart: ``zkey verify`` asserts a contribution transcript."""
+    from . import keycheck
+    return keycheck.zkey_check(r1cs, ptau, zkey, ctx or _prover().ctx)
 
 
 def fullProve(inputs: dict, circuit, zkey, rs: bytes | None = None):  # noqa: N802 (snarkjs name)
@@ -257,4 +273,4 @@ def verify_multi(jobs, schedule: str = "auto") -> list:
 
 __all__ = ["prove", "fullProve", "verify", "verify_multi", "load_vkey", "Prover", "proof_to_json", "proof_from_json", "export_verification_key",
            "vk_bytes", "public_bytes", "wtns_calculate", "r1cs_info", "read_wtns", "wtns_check",
-           "wtns_check_report"]
+           "wtns_check_report", "zkey_check"]

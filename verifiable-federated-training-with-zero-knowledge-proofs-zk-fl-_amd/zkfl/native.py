@@ -21,7 +21,7 @@ PART_BYTES = 768
 PART_LAYOUT = {"A": (0, 128), "B1": (128, 256), "B2": (256, 512), "C": (512, 640), "H": (640, 768)}
 ERRORS = {
     -1: "ZKFL_E_ARG", -2: "ZKFL_E_FORMAT", -3: "ZKFL_E_PRIME", -4: "ZKFL_E_MISMATCH",
-    -5: "ZKFL_E_DEVICE", -6: "ZKFL_E_OOM", -7: "ZKFL_E_CONSTRAINT",
+    -5: "ZKFL_E_DEVICE", -6: "ZKFL_E_OOM", -7: "ZKFL_E_CONSTRAINT", -8: "ZKFL_E_KEY",
 }
 
 _P = C.c_void_p
@@ -42,6 +42,27 @@ class R1csReport(C.Structure):
     """zkfl_r1cs_report"""
     _fields_ = [("n_failed", C.c_uint32), ("first", C.c_uint32), ("a", C.c_uint8 * 32), ("b", C.c_uint8 * 32),
                 ("c", C.c_uint8 * 32)]
+
+
+class PtauView(C.Structure):
+    """zkfl_ptau_view: the ptau's Lagrange blocks at the circuit's power and its alpha / beta points."""
+    _fields_ = [("power", C.c_uint32),
+                ("L", C.c_char_p), ("L2", C.c_char_p), ("La", C.c_char_p), ("Lb", C.c_char_p), ("H0", C.c_char_p),
+                ("L_len", C.c_size_t), ("L2_len", C.c_size_t), ("La_len", C.c_size_t), ("Lb_len", C.c_size_t),
+                ("H0_len", C.c_size_t),
+                ("alpha1", C.c_char_p), ("beta1", C.c_char_p), ("beta2", C.c_char_p)]
+
+
+# zkfl_zkey_check's checks in the order they are reported, and a check's three states
+KEY_CHECKS = ("header", "points", "coefficients", "A", "B1", "B2", "IC", "C", "H")
+KEY_STATES = ("pass", "fail", "not run")
+
+
+class ZkeyReport(C.Structure):
+    """zkfl_zkey_report"""
+    _fields_ = [("status", C.c_uint32 * len(KEY_CHECKS)),
+                ("point_section", C.c_uint32), ("point_index", C.c_uint32), ("point_count", C.c_uint32),
+                ("coef_matrix", C.c_uint32), ("coef_row", C.c_uint32), ("coef_count", C.c_uint32)]
 
 
 # every exported symbol of include/zkfl.h with (restype, argtypes)
@@ -130,6 +151,8 @@ SIGNATURES = {
     "zkfl_r1cs_check": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
                                   C.POINTER(R1csReport)]),
     "zkfl_r1cs_check_resident": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(_P), C.POINTER(R1csReport)]),
+    "zkfl_zkey_check": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, C.POINTER(PtauView), C.c_char_p, C.c_char_p,
+                                  C.POINTER(ZkeyReport)]),
 }
 
 
@@ -852,3 +875,48 @@ class R1cs:
         arr = (_P * max(1, n))(*[w.h for w in ws])
         reps = (R1csReport * max(1, n))() if reports else None
         return self._finish(lib().zkfl_r1cs_check_resident(self.ctx.h, self.h, n, arr, reps), reps, n, reports)
+
+    def check_key(self, zkey: bytes, blocks: dict, rho: bytes | None = None, sigma: bytes | None = None):
+        """zkfl_zkey_check: is ``zkey`` this circuit's Groth16 key over the ptau whose blocks are
+        given?  blocks: power, L, L2, La, Lb, H0, alpha1, beta1, beta2 (zkfl/zkey.py::ptau_blocks).
+        rho / sigma: None draws them from the OS CSPRNG; bytes (n_wires / domainSize x 32 B std) are
+        for tests and forfeit soundness.  -> KeyReport; unusable arguments raise ZkflError."""
+        keep = {k: bytes(blocks[k]) for k in ("L", "L2", "La", "Lb", "H0", "alpha1", "beta1", "beta2")}
+        view = PtauView(power=int(blocks["power"]), L_len=len(keep["L"]), L2_len=len(keep["L2"]),
+                        La_len=len(keep["La"]), Lb_len=len(keep["Lb"]), H0_len=len(keep["H0"]), **keep)
+        rep = ZkeyReport()
+        rc = lib().zkfl_zkey_check(self.ctx.h, self.h, zkey, len(zkey), C.byref(view), rho, sigma, C.byref(rep))
+        if rc not in (ZKFL_OK, -8):
+            check(rc)
+        return KeyReport(rc, rep, lib().zkfl_last_error().decode(errors="replace") if rc else "")
+
+
+class KeyReport:
+    """One key check: ``checks`` maps each of KEY_CHECKS to "pass" / "fail" / "not run"; ``point``
+    = (section, lowest bad index, count) when the points check fails, ``coef`` = (matrix, first
+    row, count) when the coefficients differ; ``error`` = the library's message naming the first
+    failing check."""
+
+    def __init__(self, rc: int, rep: ZkeyReport, error: str):
+        self.rc = rc
+        self.ok = rc == ZKFL_OK
+        self.error = error
+        self.checks = {name: KEY_STATES[rep.status[i]] for i, name in enumerate(KEY_CHECKS)}
+        self.failed = [name for name in KEY_CHECKS if self.checks[name] == "fail"]
+        self.first_failed = self.failed[0] if self.failed else None
+        self.point = ((rep.point_section, rep.point_index, rep.point_count)
+                      if self.checks["points"] == "fail" else None)
+        self.coef = ((rep.coef_matrix, rep.coef_row, rep.coef_count)
+                     if self.checks["coefficients"] == "fail" else None)
+
+    def lines(self) -> list:
+        """One line per check, as `zkey check` prints them."""
+        out = []
+        for name in KEY_CHECKS:
+            line = f"{name}: {self.checks[name]}"
+            if name == "points" and self.point:
+                line += f" (section {self.point[0]}, point {self.point[1]}, {self.point[2]} bad)"
+            if name == "coefficients" and self.coef:
+                line += f" (matrix {self.coef[0]}, row {self.coef[1]}, {self.coef[2]} rows differ)"
+            out.append(line)
+        return out

@@ -9,6 +9,9 @@ Served for `python -m zkfl <snarkjs argv>` and, through it, for the Node shim's 
   zkey contribute <in.zkey> <out.zkey> [--name=..] [-e=..]   tests/full_system_simulation.mjs:723-726
   zkey export verificationkey <c.zkey> <vkey.json>    :732-735, tests/test_secureagg.cjs:58-64
   wtns check <c.r1cs> <w.wtns>                        snarkjs's witness check (alias wchk)
+  zkey check <c.r1cs> <pot.ptau> <c.zkey>             the key check (zkfl/keycheck.py; not a snarkjs command:
+                                                      `zkey verify` / `zkv` assert a contribution transcript,
+                                                      which this does not test, and stay unserved)
 and the snarkjs aliases ptn, ptc, pt2, g16s, zkn (= groth16 setup), zkc, zkev.  The group work runs
 on the GPU (zkfl/ptau.py, zkfl/zkey.py -> libzkfl zkfl_setup_*).  Exit status 0 on success, 1 with
 an `[ERROR] snarkJS: ...` line otherwise (snarkjs's CLI convention).
@@ -103,6 +106,9 @@ def wtns_check(r1cs_path, wtns_path) -> int:
 def run(argv) -> int:
     from . import groth16, ptau, r1cs_file, zkey
     pos, opts = parse(argv)
+    if pos[:2] == ["zkey", "check"]:   # zkfl/keycheck.py: exit 0 / 1, 2 on unusable arguments
+        from . import keycheck
+        return keycheck.cli(pos[2:])
     try:
         if pos[:2] == ["wtns", "check"] and len(pos) >= 4:
             return wtns_check(pos[2], pos[3])
@@ -153,7 +159,8 @@ def run(argv) -> int:
                   "       snarkjs groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>\n"
                   "       snarkjs zkey contribute <in.zkey> <out.zkey> [--name=name] [-e=entropy]\n"
                   "       snarkjs zkey export verificationkey <circuit.zkey> <vkey.json>\n"
-                  "       snarkjs wtns check <circuit.r1cs> <witness.wtns>", file=sys.stderr)
+                  "       snarkjs wtns check <circuit.r1cs> <witness.wtns>\n"
+                  "       snarkjs zkey check <circuit.r1cs> <pot_final.ptau> <circuit.zkey>", file=sys.stderr)
             return 99
     except (ValueError, OSError) as e:
         print(f"[ERROR] snarkJS: {e}", file=sys.stderr)

@@ -234,6 +234,27 @@ def _sorted_terms(rows_of, n_rows):
     return rowptr, idx, coefs
 
 
+def ptau_blocks(cs, ptau_buf) -> dict:
+    """What a circuit's key takes from a prepared ptau, at the circuit's power: the Lagrange blocks
+    L (section 12), L2 (13), La (14), Lb (15), H0[j] = point 2j + 1 of section 12's block at
+    power + 1 (snarkjs's truncated top block when the ptau's power equals the circuit's), and
+    alpha1 / beta1 / beta2.  Shared by setup_from_ptau, which builds the key from them, and
+    zkfl/keycheck.py, which tests a key against them; raises ValueError for an unprepared or too
+    small ptau."""
+    from . import ptau as pt_mod
+    pt = pt_mod.Ptau(ptau_buf)
+    if not pt.prepared:
+        raise ValueError("Powers of tau is not prepared.")
+    n = domain_size_for(cs)
+    power = n.bit_length() - 1
+    if power > pt.power:
+        raise ValueError(f"circuit too big for this power of tau ceremony. {cs.n_constraints}*2 > 2**{pt.power}")
+    h2 = pt.lagrange(12, power + 1)
+    return dict(power=power, n=n, L=pt.lagrange(12, power), L2=pt.lagrange(13, power), La=pt.lagrange(14, power),
+                Lb=pt.lagrange(15, power), H0=b"".join(h2[64 * (2 * j + 1):64 * (2 * j + 2)] for j in range(n)),
+                alpha1=pt.points(4, 0, 1), beta1=pt.points(5, 0, 1), beta2=pt.section(6))
+
+
 def setup_from_ptau(cs, ptau_buf, ctx) -> bytes:
     """snarkjs `groth16 setup <c>.r1cs <pot>.ptau <c>_0000.zkey` (zkey_new [ext]; the harness's
     tests/full_system_simulation.mjs:713-716 and tests/test_secureagg.cjs:48-57).  cs: a
@@ -247,19 +268,12 @@ def setup_from_ptau(cs, ptau_buf, ctx) -> bytes:
     `zkey contribute` rescales delta.  alpha1 / beta1 / beta2 are the ptau's alphaTauG1[0],
     betaTauG1[0], betaG2."""
     from . import ptau as pt_mod
-    pt = pt_mod.Ptau(ptau_buf)
-    if not pt.prepared:
-        raise ValueError("Powers of tau is not prepared.")
-    n = domain_size_for(cs)
-    power = n.bit_length() - 1
-    if power > pt.power:
-        raise ValueError(f"circuit too big for this power of tau ceremony. {cs.n_constraints}*2 > 2**{pt.power}")
+    blk = ptau_blocks(cs, ptau_buf)
+    n = blk["n"]
     nv, npub, ncons = cs.n_wires, cs.n_public, cs.n_constraints
-    L = pt.lagrange(12, power)
-    L2 = pt.lagrange(13, power)
-    k_bases = L + pt.lagrange(14, power) + pt.lagrange(15, power)   # tau | alpha tau | beta tau
-    h2 = pt.lagrange(12, power + 1)
-    sec_h = b"".join(h2[64 * (2 * j + 1):64 * (2 * j + 2)] for j in range(n))
+    L, L2 = blk["L"], blk["L2"]
+    k_bases = L + blk["La"] + blk["Lb"]   # tau | alpha tau | beta tau
+    sec_h = blk["H0"]
     a_terms, b_terms, k_terms = [], [], []
     for j, (A, B, C) in enumerate(cs.cons):
         for w, c in A.items():
@@ -281,7 +295,7 @@ def setup_from_ptau(cs, ptau_buf, ctx) -> bytes:
     ic, sec_c = k[:64 * (npub + 1)], k[64 * (npub + 1):]
     hdr = struct.pack("<I", 32) + Q.to_bytes(32, "little") + struct.pack("<I", 32) + R.to_bytes(32, "little")
     hdr += struct.pack("<III", nv, npub, n)
-    hdr += (pt.points(4, 0, 1) + pt.points(5, 0, 1) + pt.section(6) + pt_mod.G2_ONE + pt_mod.G1_ONE
+    hdr += (blk["alpha1"] + blk["beta1"] + blk["beta2"] + pt_mod.G2_ONE + pt_mod.G1_ONE
             + pt_mod.G2_ONE)
     sections = [(1, struct.pack("<I", 1)), (2, hdr), (3, ic), (4, _coef_bytes(cs)), (5, sec_a), (6, sec_b1),
                 (7, sec_b2), (8, sec_c), (9, sec_h)]
