@@ -1,8 +1,9 @@
 """CPU: the witness-program compiler (zkfl/wprog.py) — the image's semantics, interpreted here
 exactly as csrc/witness.hip executes it (level by level, Montgomery-free integers), reproduce the
 oracle's circom-semantics evaluation (oracle/witness.py) on the reference circuits and inputs,
-including the fixture data/test_input_v5.json.  The GPU executor itself is compared with the
-oracle in tests/test_gpu_witness.py."""
+including the fixture data/test_input_v5.json, and on the synthetic systems of
+tests/wprog_systems.py (the ops and shapes those circuits lack).  The GPU executor itself is
+compared with the oracle in tests/test_gpu_witness.py and tests/test_gpu_wprog_ops.py."""
 import json
 import os
 import struct
@@ -12,6 +13,8 @@ import pytest
 from oracle import poseidon as op
 from oracle import witness as ow
 from zkfl import circuits, clients, wprog
+
+import wprog_systems as ws
 
 R = op.R
 RINV = pow(1 << 256, -1, R)
@@ -124,6 +127,56 @@ def test_image_semantics_match_oracle(name, params, inp):
     w, ok = interpret(img, wprog.input_bytes(b, inp))
     assert ok
     assert w == ow.evaluate(b, inp)
+
+
+@pytest.mark.parametrize("name", ws.NAMES + ws.FAIL_NAMES)
+def test_image_semantics_match_oracle_synthetic(name):
+    """The synthetic systems of tests/wprog_systems.py: the "inv" op, raw ops, every Poseidon width,
+    sparse live sets.  Inputs that violate an assert: not ok, and the wires the oracle computes
+    without its check."""
+    b, inputs = ws.system(name)
+    img = wprog.compile_program(b)
+    for x, want in zip(inputs, ws.reference(name)):
+        w, ok = interpret(img, wprog.input_bytes(b, x))
+        assert tuple(w) == want
+        assert ok == (not ws.failing_asserts(b, want))
+    if name in ws.FAIL_NAMES:
+        j, a = ws.first_failure(name)
+        assert not interpret(img, wprog.input_bytes(b, inputs[j]))[1]
+        assert ws.failing_asserts(b, ws.reference(name)[j])[0] == a
+        assert all(not ws.failing_asserts(b, w) for w in ws.reference(name)[:j])
+
+
+def test_synthetic_systems_have_the_shapes_they_claim():
+    """The properties the GPU tests rely on, read back from the compiled images."""
+    def ops_by_level(name):
+        img = wprog.compile_program(ws.system(name)[0])
+        f = struct.unpack_from("<4s13I", img, 0)
+        o = struct.calcsize("<4s13I")
+        lvp = struct.unpack_from(f"<{f[8] + 1}I", img, o)
+        o += 4 * (f[8] + 1)
+        ops = [struct.unpack_from("<4I", img, o + 16 * i) for i in range(f[7])]
+        return [ops[lvp[L]:lvp[L + 1]] for L in range(f[8])]
+
+    def count(level):
+        c = {}
+        for kind, _, _, aux in level:
+            key = (kind, aux & 0xFF) if kind == wprog.K_POS else kind
+            c[key] = c.get(key, 0) + 1
+        return c
+
+    lv = ops_by_level("mixed_level")
+    assert len(lv) == 2 and count(lv[1]) == {wprog.K_LC: 1}
+    assert count(lv[0]) == {wprog.K_LC: 70, wprog.K_MUL: 3, wprog.K_INV: 2, wprog.K_BITS: 2, (wprog.K_POS, 2): 1,
+                            (wprog.K_POS, 9): 1, (wprog.K_POS, 13): 1, (wprog.K_POS, 17): 1}
+    for t in ws.POS_WIDTHS:
+        lv = ops_by_level(f"pos_t{t}")
+        assert count(lv[0]) == {(wprog.K_POS, t): 64 // t + 1}
+        assert (count(lv[1]) == {(wprog.K_POS, t): 2}) == (t in ws.CONST_LANE_WIDTHS)
+    assert len(ops_by_level("lc_mul")) == 41
+    assert wprog.K_INV in count(ops_by_level("inv")[2])          # inv -> mul -> inv
+    assert len(ws.failing_asserts(ws.system("fail_batch")[0], ws.reference("fail_batch")[1])) == 2
+    assert ws.first_failure("fail_batch")[0] == 1
 
 
 def test_levels_respect_dependencies():
