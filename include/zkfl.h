@@ -98,6 +98,21 @@ int zkfl_zkey_load_file(zkfl_ctx* ctx, const zkfl_zkey_file* f, zkfl_key** out);
 int zkfl_zkey_file_close(zkfl_zkey_file* f);
 int zkfl_key_free(zkfl_key* key);
 int zkfl_key_info(const zkfl_key* key, uint32_t* n_vars, uint32_t* n_public, uint32_t* domain_size);
+/* How the key holds its A query.  A wire whose A and B1 bases are the same point (the
+ * S-box squares of a Poseidon circuit) would be accumulated twice per proof with the same scalar, so
+ * a key loads A as the differences D_i = A_i - B1_i wherever that has fewer bases than A itself
+ * (compared byte for byte at load; ZKFL_AB_SHARED=0 keeps A) and a proof forms A = B1 + sum w_i D_i.
+ * *d_form: 1 in that form; *shared_wires: this shard's wires with one non-zero base in both queries
+ * (0 with ZKFL_AB_SHARED=0); *a_bases: the bases of the A slot's MSM, augmentation included.  Any
+ * output may be NULL.  Proof bytes are the same in both forms. */
+int zkfl_key_ab_shared(const zkfl_key* key, uint32_t* d_form, uint32_t* shared_wires, uint32_t* a_bases);
+/* The loader's host-side partition behind it, on caller-supplied records (host only, no device):
+ * sec_a / sec_b1 = n x 64 B; counts[4] = D form chosen | shared wires | bases of the A image | bases
+ * of the D image (both with shard 0's augmentation slots: 2 and 3); in D form sidx_out (capacity
+ * n + 3) and img_out (capacity (n + 3) x 128 B, pairs A_i | B1_i) receive the image, with stand-in
+ * augmentation points of bytes 1 | 2, 3 | infinity, infinity | 3 and scalar indices n, n + 1, n + 2. */
+int zkfl_debug_ab_partition(const uint8_t* sec_a, const uint8_t* sec_b1, size_t n, uint32_t shard, uint32_t n_shards,
+                            uint32_t* counts, uint32_t* sidx_out, uint8_t* img_out);
 /* Number of proofs kept in flight by zkfl_groth16_prove_batch (1..32, default 3).  Each slot
  * owns one HIP stream and its own scratch (~0.6 GB for the 2^18 training circuit); proofs in
  * different slots overlap on the GPU.  HIP maps a process's streams onto GPU_MAX_HW_QUEUES

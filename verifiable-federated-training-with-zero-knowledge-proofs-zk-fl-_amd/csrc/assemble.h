@@ -23,6 +23,8 @@ void assemble(hipStream_t st, uint32_t n, const G1P* res, const G2P* resB2, cons
 // the same assembly in two launches: T = s pi_A + r B1 -> res[4] and pi_a; then pi_c and pi_b
 void assemble_t(hipStream_t st, G1P* res, const GlvScalar* ks, uint32_t* proof);
 void assemble_c(hipStream_t st, const G1P* res, const G2P* resB2, uint32_t* proof);
+// a key in D form: res[0] (A' - B1') += res[1] (B1'), before anything reads res[0]
+void fold_a(hipStream_t st, G1P* res);
 // out[b] = k_b P_b as the assembly computes s pi_A': pts, out affine std (zeros = infinity), ks 2 per point
 void debug_glv_mul(hipStream_t st, uint32_t n, const uint32_t* pts, const GlvScalar* ks, uint32_t* out);
 // a slot's MSM results -> its part (PART_WORDS words)

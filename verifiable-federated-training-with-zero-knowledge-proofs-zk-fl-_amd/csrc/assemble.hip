@@ -461,6 +461,17 @@ __global__ void __launch_bounds__(128) k_assemble_c(const G1P* __restrict__ res,
   }
 }
 
+// A key in D form (zkfl_key::a_diff): tail 0 finished with A' - B1', so res[0] += res[1] before
+// anything reads it -- one quad addition (complete: either may be infinity, equal or opposite).
+__global__ void __launch_bounds__(64) k_fold_a(G1P* __restrict__ res) {
+  ZK_WT(WT_ASSEMBLE);
+  ZK_LIGHT();
+  const int lane = threadIdx.x;
+  if (lane >= 4) return;
+  const G1Q a = quad_add<Q29>(g1q_from(res[0]), g1q_from(res[1]), lane);
+  if (lane == 0) res[0] = g1q_to(a);
+}
+
 // word offsets of a part's points (the encoding: assemble.h PART_WORDS)
 __device__ constexpr int PART_OFF[5] = {0, 32, 128, 160, 64};  // A', B1', C', H (G1), B2' (G2)
 
@@ -577,6 +588,8 @@ void assemble_t(hipStream_t st, G1P* res, const GlvScalar* ks, uint32_t* proof) 
 void assemble_c(hipStream_t st, const G1P* res, const G2P* resB2, uint32_t* proof) {
   hipLaunchKernelGGL(k_assemble_c, dim3(1), dim3(128), 0, st, res, resB2, proof);
 }
+
+void fold_a(hipStream_t st, G1P* res) { hipLaunchKernelGGL(k_fold_a, dim3(1), dim3(64), 0, st, res); }
 
 void debug_glv_mul(hipStream_t st, uint32_t n, const uint32_t* pts, const GlvScalar* ks, uint32_t* out) {
   hipLaunchKernelGGL(k_debug_glv_mul, dim3(n), dim3(128), 0, st, pts, ks, out);

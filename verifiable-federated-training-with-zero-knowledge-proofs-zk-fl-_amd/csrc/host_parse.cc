@@ -757,4 +757,44 @@ int inputs_from_json(const std::vector<WSignal>& sigs, const char* json, std::ve
   return ZKFL_OK;
 }
 
+void ab_partition(const uint8_t* secA, const uint8_t* secB1, size_t n, uint32_t shard, uint32_t nshards,
+                  const AbAug* aug, size_t n_aug, size_t a_aug, AbPartition& out) {
+  static const uint8_t zero[64] = {0};
+  out = AbPartition();
+  const bool aug_here = shard == 0;
+  size_t differ = 0;
+  // one counting pass decides the form, so a key that keeps the A form builds no D image
+  for (size_t i = shard; i < n; i += nshards) {
+    const uint8_t *a = secA + 64 * i, *b = secB1 + 64 * i;
+    const bool nza = memcmp(a, zero, 64) != 0;
+    if (memcmp(a, b, 64) != 0)
+      differ++;
+    else if (nza)
+      out.shared++;
+    out.n_a += nza;
+  }
+  out.n_a += aug_here ? a_aug : 0;
+  out.n_d = differ + (aug_here ? n_aug : 0);
+  out.d_form = out.n_d < out.n_a;
+  if (!out.d_form) return;
+  out.img.resize(out.n_d * 128);
+  out.sidx.reserve(out.n_d);
+  uint8_t* w = out.img.data();
+  for (size_t i = shard; i < n; i += nshards) {
+    const uint8_t *a = secA + 64 * i, *b = secB1 + 64 * i;
+    if (memcmp(a, b, 64) == 0) continue;
+    memcpy(w, a, 64);
+    memcpy(w + 64, b, 64);
+    w += 128;
+    out.sidx.push_back((uint32_t)i);
+  }
+  if (aug_here)
+    for (size_t j = 0; j < n_aug; j++) {
+      memcpy(w, aug[j].p ? aug[j].p : zero, 64);
+      memcpy(w + 64, aug[j].q ? aug[j].q : zero, 64);
+      w += 128;
+      out.sidx.push_back(aug[j].sidx);
+    }
+}
+
 }  // namespace zkfl

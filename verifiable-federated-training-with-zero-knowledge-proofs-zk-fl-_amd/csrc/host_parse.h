@@ -50,6 +50,28 @@ struct ZkeyHost {
 };
 int zkey_parse(const uint8_t* buf, size_t len, ZkeyHost& out, std::string& err);
 
+// The A query in D form (csrc/key_load.hip): D_i = A_i - B1_i per wire, so that
+// A = B1 + sum w_i D_i and a wire whose two bases are the same point (an S-box square: x * x = y)
+// costs the A MSM nothing.  secA / secB1: n records of 64 B (affine, zeros = infinity); equality is
+// byte equality.  Of the wires of this shard (i % nshards == shard) the D image keeps, in wire
+// order, the pair (A_i, B1_i) as 128 B wherever the two records differ, with sidx = i; wires with
+// equal records (both infinity included) are dropped.  On shard 0 the augmentation pairs follow
+// (a null point = infinity).  The D form is used only when it has fewer bases than the A image
+// would (its non-zero records of this shard + a_aug augmentation slots on shard 0).
+struct AbAug {
+  const uint8_t *p, *q;  // the pair's points, 64 B each (nullptr: infinity)
+  uint32_t sidx;
+};
+struct AbPartition {
+  bool d_form = false;
+  size_t shared = 0;           // wires of this shard with equal non-zero records
+  size_t n_a = 0, n_d = 0;     // bases of the A image / the D image (augmentation included)
+  std::vector<uint8_t> img;    // [n_d x 128] when d_form, else empty
+  std::vector<uint32_t> sidx;  // [n_d]
+};
+void ab_partition(const uint8_t* secA, const uint8_t* secB1, size_t n, uint32_t shard, uint32_t nshards,
+                  const AbAug* aug, size_t n_aug, size_t a_aug, AbPartition& out);
+
 // iden3 .r1cs v1 (the format zkfl/r1cs_file.py documents; it rejects what read_r1cs rejects):
 // section 1 header, section 2 constraints, optional section 3 wire-to-label map of nWires x u64.
 // With csr: the constraints as CSR rows over one term array -- the A rows, then the B rows, then

@@ -170,9 +170,24 @@ int zkey_load_parsed(zkfl_ctx* ctx, const ZkeyHost& z, size_t len, double parse_
     };
     enum { QA, QB1, QB2, QCH, NQ };
     std::vector<Img> im(NQ);
+    // A in D form where that has fewer bases (ab_partition: D_i = A_i - B1_i; A - B1 also holds
+    // (alpha1 - beta1) + r delta1 - s delta1), else as it is
+    AbPartition ab;
+    auto image_a = [&] {
+      if (ctx->opts.ab_shared) {
+        const AbAug aug[3] = {{alpha1, beta1, X + 0}, {delta1, nullptr, X + 1}, {nullptr, delta1, X + 2}};
+        ab_partition(z.secA, z.secB1, nVars, shard, nshards, aug, 3, 2, ab);
+      }
+      if (ab.d_form) {
+        im[QA].img.swap(ab.img);
+        im[QA].sidx.swap(ab.sidx);
+      } else {
+        image(im[QA], 64, z.secA, nVars, 0, {{alpha1, X + 0}, {delta1, X + 1}});
+      }
+    };
     {
       std::vector<std::thread> th;
-      th.emplace_back([&] { image(im[QA], 64, z.secA, nVars, 0, {{alpha1, X + 0}, {delta1, X + 1}}); });
+      th.emplace_back(image_a);
       th.emplace_back([&] { image(im[QB1], 64, z.secB1, nVars, 0, {{beta1, X + 0}, {delta1, X + 2}}); });
       th.emplace_back([&] { image(im[QB2], 128, z.secB2, nVars, 0, {{beta2, X + 0}, {delta2, X + 2}}); });
       th.emplace_back([&] { image_ch(im[QCH]); });
@@ -183,7 +198,7 @@ int zkey_load_parsed(zkfl_ctx* ctx, const ZkeyHost& z, size_t len, double parse_
     for (const Img& o : im) most = std::max(most, o.sidx.size());
     k->msm_c = msm_pick_c(most);
     std::vector<void*> d_imgs;
-    auto upload = [&](auto& mb, Img& o) -> hipError_t {
+    auto upload = [&](auto& mb, Img& o, bool pairs) -> hipError_t {
       hipError_t e = msm_bases_alloc(mb, o.sidx.size(), k->msm_c);
       if (e != hipSuccess || o.sidx.empty()) return e;
       void* d_img = nullptr;
@@ -191,17 +206,20 @@ int zkey_load_parsed(zkfl_ctx* ctx, const ZkeyHost& z, size_t len, double parse_
       if (e != hipSuccess) return e;
       d_imgs.push_back(d_img);
       e = hipMemcpyAsync(d_img, o.img.data(), o.img.size(), hipMemcpyHostToDevice, st);
-      if (e == hipSuccess) e = msm_bases_set(mb, static_cast<decltype(mb.bases_w)>(d_img), o.sidx.data(), X, st);
+      if (e == hipSuccess)
+        e = msm_bases_set(mb, static_cast<decltype(mb.bases_w)>(d_img), o.sidx.data(), X, st, pairs);
       return e;
     };
-    hipError_t e = upload(k->bA, im[QA]);
-    if (e == hipSuccess) e = upload(k->bB1, im[QB1]);
-    if (e == hipSuccess) e = upload(k->bB2, im[QB2]);
+    k->a_diff = ab.d_form;
+    k->ab_shared = (uint32_t)ab.shared;
+    hipError_t e = upload(k->bA, im[QA], k->a_diff);
+    if (e == hipSuccess) e = upload(k->bB1, im[QB1], false);
+    if (e == hipSuccess) e = upload(k->bB2, im[QB2], false);
     // B_i(tau) G1 and B_i(tau) G2 vanish together in an honest zkey; the sort is shared only when
     // the two index maps really are equal
     k->share_b = im[QB1].sidx == im[QB2].sidx && !im[QB1].sidx.empty();
     k->front = k->share_b && nshards == 1 && logn <= ctx->opts.small_logn;
-    if (e == hipSuccess) e = upload(k->bCH, im[QCH]);
+    if (e == hipSuccess) e = upload(k->bCH, im[QCH], false);
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;
     for (void* d : d_imgs) (void)hipFree(d);
@@ -226,6 +244,8 @@ int zkey_load_parsed(zkfl_ctx* ctx, const ZkeyHost& z, size_t len, double parse_
         fprintf(f, ", \"%s_ms\": %.3f", m.first.c_str(), m.second);
         total += m.second;
       }
+      fprintf(f, ", \"a_form\": \"%s\", \"ab_shared\": %u, \"a_bases\": %zu", k->a_diff ? "D" : "A", k->ab_shared,
+              k->bA.n);
       fprintf(f, ", \"total_ms\": %.3f}\n", total);
       fclose(f);
     }
@@ -326,6 +346,35 @@ int zkfl_key_info(const zkfl_key* key, uint32_t* n_vars, uint32_t* n_public, uin
   if (n_vars) *n_vars = key->nVars;
   if (n_public) *n_public = key->nPub;
   if (domain_size) *domain_size = key->n;
+  return ZKFL_OK;
+}
+
+int zkfl_key_ab_shared(const zkfl_key* key, uint32_t* d_form, uint32_t* shared_wires, uint32_t* a_bases) {
+  if (!key) return fail(ZKFL_E_ARG, "null key");
+  if (d_form) *d_form = key->a_diff ? 1u : 0u;
+  if (shared_wires) *shared_wires = key->ab_shared;
+  if (a_bases) *a_bases = (uint32_t)key->bA.n;
+  return ZKFL_OK;
+}
+
+int zkfl_debug_ab_partition(const uint8_t* sec_a, const uint8_t* sec_b1, size_t n, uint32_t shard, uint32_t n_shards,
+                            uint32_t* counts, uint32_t* sidx_out, uint8_t* img_out) {
+  if ((n && (!sec_a || !sec_b1)) || !counts || n_shards < 1 || shard >= n_shards || n > 0x7FFFFFF0u)
+    return fail(ZKFL_E_ARG, "ab_partition: bad arguments");
+  // the loader's augmentation slots, with recognisable points: (1.., 2..), (3.., inf), (inf, 3..)
+  uint8_t pt[3][64];
+  for (int j = 0; j < 3; j++) memset(pt[j], j + 1, 64);
+  const AbAug aug[3] = {{pt[0], pt[1], (uint32_t)n}, {pt[2], nullptr, (uint32_t)n + 1}, {nullptr, pt[2], (uint32_t)n + 2}};
+  AbPartition ab;
+  ab_partition(sec_a, sec_b1, n, shard, n_shards, aug, 3, 2, ab);
+  counts[0] = ab.d_form ? 1u : 0u;
+  counts[1] = (uint32_t)ab.shared;
+  counts[2] = (uint32_t)ab.n_a;
+  counts[3] = (uint32_t)ab.n_d;
+  if (ab.d_form) {
+    if (sidx_out) memcpy(sidx_out, ab.sidx.data(), ab.sidx.size() * 4);
+    if (img_out) memcpy(img_out, ab.img.data(), ab.img.size());
+  }
   return ZKFL_OK;
 }
 

@@ -134,20 +134,27 @@ static __global__ void __launch_bounds__(256) k_msm_to_m29(Fq* __restrict__ a, s
 // ---------------------------------------------------------------------------
 // Key-load-time window expansion: out[i*W + j] = 2^(c j) * in[i]  (affine)
 // ---------------------------------------------------------------------------
-template <class F, int C>
+// PAIR: in holds n pairs (P_i, Q_i) and the base is P_i - Q_i (the A query in D form, key_load.hip):
+// one mixed addition ahead of the doublings, complete -- either point may be infinity, P = Q gives
+// infinity (every window copy then is), P = -Q a doubling.
+template <class F, int C, bool PAIR = false>
 __global__ void __launch_bounds__(64) k_msm_expand(const Affine<F>* __restrict__ in, size_t n, Affine<F>* __restrict__ out) {
   constexpr int W = msm_w_of(C);
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   using T = typename F::T;
-  Affine<F> p = in[i];
-  if (aff_is_inf(p)) {
-    for (int j = 0; j < W; j++) out[i * W + j] = p;
+  XYZZ<F> acc = xyzz_from_affine<F>(in[PAIR ? 2 * i : i]);
+  if constexpr (PAIR) {
+    const Affine<F> q = in[2 * i + 1];
+    if (!aff_is_inf(q)) acc = xyzz_madd<F>(acc, aff_neg<F>(q));
+  }
+  if (xyzz_is_inf(acc)) {
+    const Affine<F> z = {F::zero(), F::zero()};
+    for (int j = 0; j < W; j++) out[i * W + j] = z;
     return;
   }
   // Keep the W window copies in XYZZ in the output slots' scratch (global), with a
   // Montgomery batch inversion of their ZZZ over the 16 copies.
-  XYZZ<F> acc = xyzz_from_affine<F>(p);
   T pref[W];
   XYZZ<F> pts[W];
   for (int j = 0; j < W; j++) {
@@ -644,10 +651,12 @@ void msm_bases_free(MsmBases<F>& b) {
 }
 
 // Expand b.n affine bases (device pointer) into the window table; h_sidx (host, b.n entries)
-// is the scalar index map or nullptr for identity.
+// is the scalar index map or nullptr for identity.  pairs (G1 only): d_bases holds b.n pairs
+// (P_i, Q_i), base i is P_i - Q_i.
 template <class F>
 hipError_t msm_bases_set(MsmBases<F>& b, const Affine<F>* d_bases, const uint32_t* h_sidx, uint32_t extra_start,
-                         hipStream_t st) {
+                         hipStream_t st, bool pairs) {
+  if (pairs && !std::is_same<F, FqOps>::value) return hipErrorInvalidValue;
   // identity maps never address the extra slots (H has domainSize > nVars entries on small circuits)
   b.extra_start = h_sidx ? extra_start : 0xFFFFFFFFu;
   if (h_sidx && b.n) {
@@ -656,8 +665,15 @@ hipError_t msm_bases_set(MsmBases<F>& b, const Affine<F>* d_bases, const uint32_
   }
   if (b.n)
     ZK_CHECK(msm_with_c(b.c, [&](auto cc) {
-      hipLaunchKernelGGL((k_msm_expand<F, decltype(cc)::value>), dim3(zk_grid(b.n, 64)), dim3(64), 0, st, d_bases,
-                         b.n, b.bases_w);
+      constexpr int C = decltype(cc)::value;
+      if constexpr (std::is_same<F, FqOps>::value) {
+        if (pairs) {
+          hipLaunchKernelGGL((k_msm_expand<F, C, true>), dim3(zk_grid(b.n, 64)), dim3(64), 0, st, d_bases, b.n,
+                             b.bases_w);
+          return hipSuccess;
+        }
+      }
+      hipLaunchKernelGGL((k_msm_expand<F, C>), dim3(zk_grid(b.n, 64)), dim3(64), 0, st, d_bases, b.n, b.bases_w);
       return hipSuccess;
     }));
   const size_t nfq = b.n * msm_w_of(b.c) * (sizeof(Affine<F>) / sizeof(Fq));

@@ -199,7 +199,7 @@ template <class F>
 hipError_t msm_bases_alloc(MsmBases<F>& b, size_t n, int c);
 template <class F>
 hipError_t msm_bases_set(MsmBases<F>& b, const Affine<F>* src, const uint32_t* h_sidx, uint32_t extra_start,
-                         hipStream_t st);
+                         hipStream_t st, bool pairs = false);
 template <class F>
 void msm_bases_free(MsmBases<F>& b);
 template <class F>
@@ -241,7 +241,7 @@ hipError_t msm_accumulate_sorted_multi(const MsmBases<F>* const* b, const uint16
 // The entry points above for one curve: X = `extern template` here, `template` in the curve's unit.
 #define ZKFL_MSM_API(X, F)                                                                                     \
   X hipError_t msm_bases_alloc<F>(MsmBases<F>&, size_t, int);                                                  \
-  X hipError_t msm_bases_set<F>(MsmBases<F>&, const Affine<F>*, const uint32_t*, uint32_t, hipStream_t);       \
+  X hipError_t msm_bases_set<F>(MsmBases<F>&, const Affine<F>*, const uint32_t*, uint32_t, hipStream_t, bool); \
   X void msm_bases_free<F>(MsmBases<F>&);                                                                      \
   X hipError_t msm_scratch_alloc<F>(MsmScratch<F>&, size_t, int, hipStream_t);                                 \
   X void msm_scratch_free<F>(MsmScratch<F>&);                                                                  \

@@ -49,6 +49,7 @@ struct SchedOpts {
   bool lowlat = true;     // ZKFL_LOWLAT: a batch of one takes the latency schedule
   bool fast_wsum = true;  // ZKFL_FAST_WSUM: shorter-chain bucket reduction (latency schedule, small keys)
   int small_logn = 16;    // ZKFL_SMALL_LOGN: a key with a domain <= 2^small_logn is a small key
+  bool ab_shared = true;  // ZKFL_AB_SHARED: keys load their A query in D form where that has fewer bases
 };
 
 struct zkfl_ctx {
@@ -135,6 +136,13 @@ struct zkfl_key {
   // runs the C + H MSM twice, once with a zero h (C alone) and once with a zero witness (H alone),
   // so the key holds no separate C and H bases (they were ~0.5 GB of expanded bases per key at 2^18)
   Fr* dbg_zero = nullptr;
+  // The A query in D form (ab_partition, host_parse.h): bA holds D_i = A_i - B1_i of the wires whose
+  // two bases differ (and alpha1 - beta1, delta1 with r, -delta1 with s), so its MSM yields A - B1
+  // and every proof adds B1's result to it (fold_a) before anything reads res[0].  The wires that
+  // share a base -- the S-box squares, a third of A on the Poseidon-heavy circuits -- are then
+  // accumulated once per proof, in B1, instead of twice.
+  bool a_diff = false;
+  uint32_t ab_shared = 0;  // this shard's wires with the same non-zero base in A and B1
   bool share_b = false;  // B1 and B2 have the same base index map: one digit sort serves both
   // small keys (domain <= 2^SchedOpts::small_logn, config 5's circuits): a proof sorts A, B1 and
   // C + H in the same four launches and accumulates them in one (msm_sort_multi /

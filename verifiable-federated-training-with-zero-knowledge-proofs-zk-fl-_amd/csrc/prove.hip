@@ -385,9 +385,11 @@ hipError_t b2_from_b1_sort(zkfl_key* k, ProofSlot* s, const MsmScratch<FqOps>& s
 
 // Step: what leaves a one-stream schedule -- a split proof's part and its download, a proof's
 // assembly (pi_a, pi_b, pi_c) into the pinned buffer, nothing for the parity hook (its caller
-// reads res, resB2 and h).
-int finish(ProofSlot* s, const ProofPlan& p, Profiler* prof) {
+// reads res, resB2 and h).  A key in D form first turns tail 0's A' - B1' into A' (every mode reads
+// res[0]).
+int finish(const zkfl_key* k, ProofSlot* s, const ProofPlan& p, Profiler* prof) {
   hipStream_t st = s->st_main;
+  if (k->a_diff) fold_a(st, s->res);
   if (p.mode == ProofMode::SplitPart) {
     part_out(st, s->res, s->resB2, s->d_parts);
     HIP_TRY(hipMemcpyAsync(s->pinned + 512, s->d_parts, PART_WORDS * 4, hipMemcpyDeviceToHost, st), "download part");
@@ -407,7 +409,7 @@ int finish(ProofSlot* s, const ProofPlan& p, Profiler* prof) {
 //          wait(B2, T), k_assemble_c (pi_c, pi_b) into the pinned buffer
 //   lat0 : wait(ev ready) B sort (own scratch) [ev B sorted] B2 + its tail [ev B2]
 //   lat1 : wait(ev B sorted) B1, A (sort into its own scratch + accumulate), the tails of A and
-//          B1, k_assemble_t (T = s pi_A + r B1, pi_a) [ev T]
+//          B1, [A' += B1': a key in D form], k_assemble_t (T = s pi_A + r B1, pi_a) [ev T]
 // Same proof bytes as the one-stream schedules (k_assemble_t / _c form the same points).  The
 // round-4 schedule ran A and B1 on the main stream ahead of ABC / NTT (4.10 vs 4.16 ms then); with
 // the row assembly and the divsteps inversions the overlap wins: 3.586 vs 3.712 ms, 3 same-box
@@ -438,6 +440,7 @@ int run_lowlat(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Pro
                                    "msm_accumulate_g1"), "msm B1");
   HIP_TRY(msm_accumulate(k->bA, s->g1s_a, s->g1t[0], W, E, sa, prof, "msm_accumulate_g1"), "msm A");
   HIP_TRY(msm_tails(tails, outs, 2, sa, p.fast_wsum), "msm tails A, B1");
+  if (k->a_diff) fold_a(sa, s->res);  // D form: A' = (A' - B1') + B1'
   assemble_t(sa, s->res, glv_halves(s), proof_out(s));
   HIP_TRY(hipEventRecord(ev_t, sa), "event");
   // main: ABC / NTT / h, C + H and its tail, then pi_c and pi_b
@@ -477,7 +480,7 @@ int run_front(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Prof
   MsmTail<Fq2Ops>* t2 = &s->g2t;
   G2P* o2 = s->resB2;
   HIP_TRY(msm_tails_joint(tails, outs, 3, &t2, &o2, 1, st, p.fast_wsum), "msm tails (G1 + G2)");
-  return finish(s, p, prof);
+  return finish(k, s, p, prof);
 }
 
 // Every other proof, a serial chain on the slot's one stream:
@@ -525,7 +528,7 @@ int run_chain(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Prof
     HIP_TRY(msm_tails_joint(tails, outs, ntails, &t2, &o2, 1, st, p.fast_wsum), "msm tails (G1 + G2)");
   else
     HIP_TRY(msm_tails(tails, outs, ntails, st, p.fast_wsum), "msm tails");
-  return finish(s, p, prof);
+  return finish(k, s, p, prof);
 }
 
 // The device work of one proof, launch by launch: start, then its plan's schedule.

@@ -262,6 +262,7 @@ int zkfl_ctx_create(int device, zkfl_ctx** out) {
   ctx->opts.lowlat = env("ZKFL_LOWLAT", 1) != 0;
   ctx->opts.fast_wsum = env("ZKFL_FAST_WSUM", 1) != 0;
   ctx->opts.small_logn = env("ZKFL_SMALL_LOGN", 16);
+  ctx->opts.ab_shared = env("ZKFL_AB_SHARED", 1) != 0;
   hipError_t e = hipStreamCreateWithFlags(&ctx->st, hipStreamNonBlocking);
   if (e != hipSuccess) {
     delete ctx;

@@ -88,6 +88,9 @@ SIGNATURES = {
     "zkfl_groth16_assemble": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.c_char_p, C.c_char_p, _U8P]),
     "zkfl_key_free": (C.c_int, [_P]),
     "zkfl_key_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "zkfl_key_ab_shared": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "zkfl_debug_ab_partition": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _U8P]),
     "zkfl_key_set_slots": (C.c_int, [_P, C.c_int]),
     "zkfl_groth16_prove": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, C.c_char_p, _U8P, _U8P,
                                      C.POINTER(C.c_size_t)]),
@@ -616,6 +619,13 @@ class ProvingKey:
             self.close()
         except Exception:
             pass
+
+    def ab_shared(self) -> dict:
+        """How the key holds its A query (zkfl_key_ab_shared): form "D" (A = B1 + sum w_i (A_i - B1_i))
+        or "A", this shard's wires with one base in both queries, and the A slot's base count."""
+        d, sh, nb = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(lib().zkfl_key_ab_shared(self.h, C.byref(d), C.byref(sh), C.byref(nb)))
+        return {"form": "D" if d.value else "A", "shared_wires": sh.value, "a_bases": nb.value}
 
     def set_slots(self, slots: int):
         """Proofs kept in flight by prove_batch (each slot = 3 HIP streams + scratch)."""
