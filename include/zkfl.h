@@ -204,6 +204,17 @@ int zkfl_debug_g1_glv_mul(zkfl_ctx* ctx, size_t n, const uint8_t* points, const 
  * *count; op 0: free.  tools/wtrace.py reads them. */
 int zkfl_debug_wtrace(zkfl_ctx* ctx, int op, uint32_t cap, void* out, uint32_t* count);
 
+/* The proof's coset transform on a caller's batch, under any of its schedules (parity hook):
+ * zkfl_ntt_coset on nvec (1..3) vectors of 2^logn (logn 1..27) std-form elements, in place, as one
+ * batched call the way the prover makes it.  Vector v starts at element v * vstride (vstride >= 2^logn);
+ * data holds ((nvec - 1) * vstride + 2^logn) * 32 bytes, and the elements between the vectors come
+ * back unchanged.  col_max: the stages above the 1024-element LDS tile (logn - 10 of them) run as
+ * one column pass when there are at most col_max, as radix-2 global passes with unfused LDS
+ * passes otherwise; < 0 = the prover's default (10: column passes up to 2^20), 0 = the schedule of
+ * the domains above 2^20 at any logn > 10; above 10 is ZKFL_E_ARG.  Every schedule gives the same
+ * bytes. */
+int zkfl_debug_ntt_coset(zkfl_ctx* ctx, uint8_t* data, uint32_t logn, uint32_t nvec, size_t vstride, int col_max);
+
 /* Stand-alone primitives (parity tests).  bases: mont affine; scalars: std, n x 32 B. */
 int zkfl_msm_g1(zkfl_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, uint8_t out[64]);
 int zkfl_msm_g2(zkfl_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, uint8_t out[128]);

@@ -12,6 +12,9 @@
  *
  * Exported: ref_prove(zkey, zkey_len, wtns, wtns_len, rs(64 B) , proof_out(256 B), threads)
  *           -> 0 ok / <0 error.   Proof layout = include/zkfl.h (std affine, LE).
+ *           ref_coset_ntt(data, power, threads): the coset transform of the proof alone, in place
+ *           (the checker of zkfl_ntt_coset / zkfl_debug_ntt_coset at sizes the Python oracle is
+ *           too slow for).
  */
 #include <omp.h>
 #include <stdint.h>
@@ -428,6 +431,52 @@ static void g2_to_std_aff(uint8_t* out, const g2_jac* p) {
   memcpy(out + 64, y.c0.v, 32); memcpy(out + 96, y.c1.v, 32);
 }
 
+/* In place, Montgomery form: evaluations on the 2^power domain -> evaluations on the odd coset
+ * (inverse ntt, scale by inc^i / n, forward ntt), as snarkjs's ifft + batchApplyKey(inc) + fft. */
+static void coset_ntt_mont(fe* x, int power) {
+  const size_t n = (size_t)1 << power;
+  fe wf = root_std(power, 0), wi = root_std(power, 1);
+  fe inc = power == 28 ? (fe){{25, 0, 0, 0}} : root_std(power + 1, 0);
+  if (power == 28) to_mont_r(&inc);
+  fe ninv = {{n, 0, 0, 0}};
+  to_mont_r(&ninv);
+  {
+    uint64_t e[4];
+    memcpy(e, RP, 32);
+    e[0] -= 2;
+    fpow(&ninv, &ninv, e, RP, RINV, &R_ONE);
+  }
+  ntt(x, n, &wi);
+#pragma omp parallel for schedule(static)
+  for (size_t i = 0; i < n; i++) {
+    fe f;
+    r_pow_u64(&f, &inc, i);
+    RMUL(&f, &f, &ninv);
+    RMUL(&x[i], &x[i], &f);
+  }
+  ntt(x, n, &wf);
+}
+
+/* The coset transform alone, in place on 2^power elements of 32 B little-endian standard form
+ * (each < r): the conventions of zkfl_ntt_coset (include/zkfl.h). */
+int ref_coset_ntt(uint8_t* data, uint32_t power, int threads) {
+  if (!data || power < 1 || power > 27) return -1;
+  init_consts();
+  if (threads > 0) omp_set_num_threads(threads);
+  const size_t n = (size_t)1 << power;
+  fe* x = malloc(n * sizeof(fe));
+  if (!x) return -3;
+  memcpy(x, data, n * 32);
+#pragma omp parallel for schedule(static)
+  for (size_t i = 0; i < n; i++) to_mont_r(&x[i]);
+  coset_ntt_mont(x, (int)power);
+#pragma omp parallel for schedule(static)
+  for (size_t i = 0; i < n; i++) from_mont_r(&x[i]);
+  memcpy(data, x, n * 32);
+  free(x);
+  return 0;
+}
+
 /* Full proof plus the deterministic core for parity checks: h_out (n x 32 B std, the H-MSM
  * scalars) and msm_out (A 64 | B1 64 | B2 128 | C 64 | H 64, std affine, without the
  * alpha/beta/delta/r/s terms), both nullable: the layout of zkfl_debug_prove_parts. */
@@ -468,29 +517,7 @@ int ref_prove_ex(const uint8_t* zk, size_t zlen, const uint8_t* wt, size_t wlen,
   for (uint32_t i = 0; i < n; i++) RMUL(&C[i], &A[i], &B[i]);
 
   /* coset evaluations */
-  fe wf = root_std(power, 0), wi = root_std(power, 1);
-  fe inc = power == 28 ? (fe){{25, 0, 0, 0}} : root_std(power + 1, 0);
-  if (power == 28) to_mont_r(&inc);
-  fe ninv = {{n, 0, 0, 0}};
-  to_mont_r(&ninv);
-  {
-    uint64_t e[4];
-    memcpy(e, RP, 32);
-    e[0] -= 2;
-    fpow(&ninv, &ninv, e, RP, RINV, &R_ONE);
-  }
-  for (int v = 0; v < 3; v++) {
-    fe* x = abc + (size_t)v * n;
-    ntt(x, n, &wi);
-#pragma omp parallel for schedule(static)
-    for (uint32_t i = 0; i < n; i++) {
-      fe f;
-      r_pow_u64(&f, &inc, i);
-      RMUL(&f, &f, &ninv);
-      RMUL(&x[i], &x[i], &f);
-    }
-    ntt(x, n, &wf);
-  }
+  for (int v = 0; v < 3; v++) coset_ntt_mont(abc + (size_t)v * n, power);
   fe* hs = malloc((size_t)n * sizeof(fe));
 #pragma omp parallel for schedule(static)
   for (uint32_t i = 0; i < n; i++) {

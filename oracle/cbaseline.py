@@ -25,6 +25,8 @@ def lib():
                                    C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
         L.ref_msm_g1.restype = C.c_int
         L.ref_msm_g1.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_int]
+        L.ref_coset_ntt.restype = C.c_int
+        L.ref_coset_ntt.argtypes = [C.POINTER(C.c_uint8), C.c_uint32, C.c_int]
         for nm in ("ref_g1_gen_mul", "ref_g2_gen_mul"):
             f = getattr(L, nm)
             f.restype = C.c_int
@@ -59,6 +61,20 @@ def msm_g1(bases: bytes, scalars: bytes, threads: int = 0) -> bytes:
     out = (C.c_uint8 * 64)()
     lib().ref_msm_g1(bases, scalars, len(scalars) // 32, out, threads)
     return bytes(out)
+
+
+def coset_ntt(data: bytes, threads: int = 0) -> bytes:
+    """2^k elements (32 B little-endian standard form, each < r), evaluations on the domain ->
+    evaluations on the odd coset: the conventions of zkfl_ntt_coset (include/zkfl.h), k = 1..27."""
+    n = len(data) // 32
+    power = n.bit_length() - 1
+    if len(data) != 32 * n or n < 2 or n != 1 << power or power > 27:
+        raise ValueError("coset_ntt: need 2^k elements of 32 bytes, k = 1..27")
+    buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
+    rc = lib().ref_coset_ntt(buf, power, threads)
+    if rc:
+        raise RuntimeError(f"ref_coset_ntt failed: {rc}")
+    return bytes(buf)
 
 
 def _cgroup_quota_cores():

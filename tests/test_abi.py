@@ -16,7 +16,7 @@ def _declared():
 def test_header_declares_expected_surface():
     names = _declared()
     for must in ("zkfl_zkey_load", "zkfl_groth16_prove", "zkfl_groth16_prove_batch", "zkfl_msm_g1",
-                 "zkfl_msm_g2", "zkfl_ntt_coset", "zkfl_setup_g1_gen_mul", "zkfl_last_error"):
+                 "zkfl_msm_g2", "zkfl_ntt_coset", "zkfl_debug_ntt_coset", "zkfl_setup_g1_gen_mul", "zkfl_last_error"):
         assert must in names
 
 
@@ -33,6 +33,9 @@ def test_version_and_error_paths_without_device():
     # null-argument paths return ZKFL_E_ARG without touching a device
     assert L.zkfl_key_info(None, None, None, None) == -1
     assert L.zkfl_ctx_set_profiling(None, 1) == -1
+    buf = (ctypes.c_uint8 * 64)()
+    assert L.zkfl_ntt_coset(None, buf, 1) == -1
+    assert L.zkfl_debug_ntt_coset(None, buf, 1, 1, 2, -1) == -1
 
 
 def test_glv_split_host():

@@ -29,6 +29,30 @@ def test_c_msm_matches_python(cb):
     assert bn.g1_from_bytes_std(out) == bn.msm(pts, ss)
 
 
+@pytest.mark.parametrize("logn", range(1, 11))
+def test_c_coset_ntt_matches_python(cb, logn):
+    """ref_coset_ntt (the checker of the GPU NTT at sizes the Python oracle is too slow for) against
+    og.coset_evals, bit for bit: random vectors with the edge elements (0, 1, r - 1, r - 2, 2^253,
+    (r - 1) / 2) in front, and the whole-vector edge inputs (zero, all r - 1, a constant, 0 / r - 1
+    alternating); one thread and several give the same bytes."""
+    import ntt_vectors as nv
+    vecs = dict(nv.edge_vecs(logn), random_a=nv.random_vec(logn, 100 + logn), random_b=nv.random_vec(logn, 200 + logn))
+    assert set(vecs) >= {"zero", "all_r_minus_1", "constant", "alternating"}
+    for name, data in vecs.items():
+        want = b"".join(nv.le(x) for x in og.coset_evals(nv.ints(data)))
+        assert cb.coset_ntt(data, threads=1) == want, name
+        assert cb.coset_ntt(data, threads=3) == want, name
+    assert cb.coset_ntt(vecs["zero"]) == vecs["zero"]
+    assert cb.coset_ntt(vecs["constant"]) == vecs["constant"]   # a constant polynomial
+
+
+def test_c_coset_ntt_rejects_bad_sizes(cb):
+    for bad in (b"", bytes(32), bytes(96), bytes(65)):
+        with pytest.raises(ValueError):
+            cb.coset_ntt(bad)
+    assert cb.lib().ref_coset_ntt(None, 3, 1) == -1
+
+
 @pytest.mark.parametrize("circ", [("poseidon_hash2",), ("sgd_verified", 8, 4, 3, 1000)])
 def test_c_prove_matches_python(cb, circ):
     from oracle_backend import COraclePoints, OraclePoints

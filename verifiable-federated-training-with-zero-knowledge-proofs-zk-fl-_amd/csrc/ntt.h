@@ -17,12 +17,19 @@
 
 namespace zkfl {
 
+// The column pass (k_ntt_cols) takes up to this many stages above the LDS tile in one kernel.
+constexpr int NTT_COL_TILE_LOG = 10;
+
 struct NttPlan {
   int logn = 0;
   size_t n = 0;
   Fr* tw_fwd = nullptr;   // [n/2] forward root powers
   Fr* tw_inv = nullptr;   // [n/2] inverse root powers
   Fr* coset = nullptr;    // [n] inc^{bitrev(p)} / n
+  // The stages above the LDS tile (logn - 10 of them) run as one column pass when there are at most
+  // col_max, as radix-2 global passes otherwise: 0 .. NTT_COL_TILE_LOG.  Only the parity hook
+  // zkfl_debug_ntt_coset lowers it, to run the large-domain schedule at small sizes.
+  int col_max = NTT_COL_TILE_LOG;
 };
 
 hipError_t ntt_plan_alloc(NttPlan& pl, int logn, hipStream_t st);

@@ -252,7 +252,6 @@ __global__ void __launch_bounds__(256) k_ntt_lds4(Fr* __restrict__ a, size_t n, 
 // 2^(logn-k).  One workgroup takes NTT_COL_TILE / 2^k consecutive columns (rows of consecutive
 // elements are contiguous in memory), runs the k stages in LDS and writes back: one global pass
 // instead of k radix-2 passes.
-constexpr int NTT_COL_TILE_LOG = 10;
 constexpr int NTT_COL_TILE = 1 << NTT_COL_TILE_LOG;
 template <bool DIF>
 __global__ void __launch_bounds__(256) k_ntt_cols(Fr* __restrict__ a, int logn, int k, const Fr* __restrict__ tw,
@@ -263,7 +262,7 @@ __global__ void __launch_bounds__(256) k_ntt_cols(Fr* __restrict__ a, int logn, 
   const size_t n = (size_t)1 << logn;
   const int lowlog = logn - k;                 // column stride 2^lowlog
   const size_t M = (size_t)1 << k;             // elements per column
-  const size_t C = (size_t)NTT_COL_TILE >> k;  // columns per workgroup (k <= 11)
+  const size_t C = (size_t)NTT_COL_TILE >> k;  // columns per workgroup (k <= NTT_COL_TILE_LOG = 10)
   const size_t groups = ((size_t)1 << lowlog) / C;
   const size_t v = blockIdx.x / groups;
   if (v >= (size_t)nvec) return;
@@ -324,6 +323,7 @@ __global__ void k_fr_to_mont_one(Fr* out, Fr in) { *out = fp_to_mont(in); }
 hipError_t ntt_plan_alloc(NttPlan& pl, int logn, hipStream_t st) {
   pl.logn = logn;
   pl.n = (size_t)1 << logn;
+  pl.col_max = NTT_COL_TILE_LOG;
   size_t half = pl.n > 1 ? pl.n / 2 : 1;
   ZK_CHECK(hipMalloc(&pl.tw_fwd, half * sizeof(Fr)));
   ZK_CHECK(hipMalloc(&pl.tw_inv, half * sizeof(Fr)));
@@ -357,13 +357,14 @@ void ntt_plan_free(NttPlan& pl) {
 
 // DIF pass of the inverse transform (natural -> bit-reversed), 1/n and the coset scale fused
 // into the last (LDS) pass when `scale` is given.  The stages above the LDS tile run as one
-// column pass (logn <= 21) or as radix-2 global passes (larger domains).
+// column pass (at most pl.col_max of them: logn <= 20 by default) or as radix-2 global passes
+// (larger domains).
 static hipError_t ntt_dif(const NttPlan& pl, Fr* d, const Fr* tw, int nvec, size_t vstride, const Fr* scale,
                           hipStream_t st) {
   const size_t n = pl.n;
   const int logt = pl.logn < NTT_LDS_LOG ? pl.logn : NTT_LDS_LOG;
   const int top = pl.logn - logt;
-  const int kcol = top <= NTT_COL_TILE_LOG ? top : 0;  // one column pass, or radix-2 passes (logn > 21)
+  const int kcol = top <= pl.col_max ? top : 0;  // one column pass, or radix-2 passes (logn > 20 by default)
   const size_t nb = (n >> 1) * nvec;
   for (int s = 0; s < top - kcol; s++) {
     size_t half = n >> (s + 1);
@@ -390,7 +391,7 @@ static hipError_t ntt_dit(const NttPlan& pl, Fr* d, const Fr* tw, int nvec, size
   const size_t n = pl.n;
   const int logt = pl.logn < NTT_LDS_LOG ? pl.logn : NTT_LDS_LOG;
   const int top = pl.logn - logt;
-  const int kcol = top <= NTT_COL_TILE_LOG ? top : 0;
+  const int kcol = top <= pl.col_max ? top : 0;
   const size_t nb = (n >> 1) * nvec;
   if (logt > 0 && NTT_RADIX4)
     hipLaunchKernelGGL(k_ntt_lds4<false>, dim3((unsigned)((n >> logt) * nvec)), dim3(256), 0, st, d, n, logt, tw,
@@ -418,7 +419,7 @@ static hipError_t ntt_dit(const NttPlan& pl, Fr* d, const Fr* tw, int nvec, size
 hipError_t ntt_coset_shift(const NttPlan& pl, Fr* d, int nvec, size_t vstride, hipStream_t st) {
   const int logt = pl.logn < NTT_LDS_LOG ? pl.logn : NTT_LDS_LOG;
   const int top = pl.logn - logt;
-  if (!NTT_LDS_PAIR || NTT_RADIX4 || logt == 0 || top == 0 || top > NTT_COL_TILE_LOG) {
+  if (!NTT_LDS_PAIR || NTT_RADIX4 || logt == 0 || top == 0 || top > pl.col_max) {
     ZK_CHECK(ntt_dif(pl, d, pl.tw_inv, nvec, vstride, pl.coset, st));
     return ntt_dit(pl, d, pl.tw_fwd, nvec, vstride, st);
   }

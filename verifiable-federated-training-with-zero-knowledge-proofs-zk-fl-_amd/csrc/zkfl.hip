@@ -399,30 +399,38 @@ int zkfl_msm_g2(zkfl_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, siz
   return run_msm_primitive<Fq2Ops>(ctx, bases, scalars, n, out);
 }
 
-int zkfl_ntt_coset(zkfl_ctx* ctx, uint8_t* data, uint32_t logn) {
-  if (!ctx || !data || logn < 1 || logn > 27) return fail(ZKFL_E_ARG, "ntt: bad args");
+int zkfl_debug_ntt_coset(zkfl_ctx* ctx, uint8_t* data, uint32_t logn, uint32_t nvec, size_t vstride, int col_max) {
+  if (!ctx || !data || logn < 1 || logn > 27 || nvec < 1 || nvec > 3 || col_max > NTT_COL_TILE_LOG)
+    return fail(ZKFL_E_ARG, "ntt: bad args");
+  const size_t n = (size_t)1 << logn;
+  if (vstride < n || vstride > ((size_t)1 << 32)) return fail(ZKFL_E_ARG, "ntt: bad stride");
   hipStream_t st = ctx->st;
   NttPlan pl;
   Fr* d = nullptr;
-  const size_t n = (size_t)1 << logn;
+  const size_t bytes = ((size_t)(nvec - 1) * vstride + n) * 32;
   int rc = ZKFL_OK;
   hipError_t e = ntt_plan_alloc(pl, (int)logn, st);
-  if (e == hipSuccess) e = hipMalloc(&d, n * 32);
-  if (e == hipSuccess) e = hipMemcpyAsync(d, data, n * 32, hipMemcpyHostToDevice, st);
+  if (col_max >= 0) pl.col_max = col_max;
+  if (e == hipSuccess) e = hipMalloc(&d, bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(d, data, bytes, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
-    fr_std_to_mont(st, d, n);
-    e = ntt_coset_shift(pl, d, 1, n, st);
+    for (uint32_t v = 0; v < nvec; v++) fr_std_to_mont(st, d + v * vstride, n);  // the gaps stay as they are
+    e = ntt_coset_shift(pl, d, (int)nvec, vstride, st);
   }
   if (e == hipSuccess) {
-    fr_mont_to_std(st, d, n);
+    for (uint32_t v = 0; v < nvec; v++) fr_mont_to_std(st, d + v * vstride, n);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(data, d, n * 32, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(data, d, bytes, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) rc = hip_fail(e, "ntt");
   ntt_plan_free(pl);
   if (d) (void)hipFree(d);
   return rc;
+}
+
+int zkfl_ntt_coset(zkfl_ctx* ctx, uint8_t* data, uint32_t logn) {
+  return zkfl_debug_ntt_coset(ctx, data, logn, 1, logn <= 27 ? (size_t)1 << logn : 0, -1);
 }
 
 // Ceremony primitives (csrc/setup.hip)

@@ -105,6 +105,7 @@ SIGNATURES = {
     "zkfl_msm_g1": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_size_t, _U8P]),
     "zkfl_msm_g2": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_size_t, _U8P]),
     "zkfl_ntt_coset": (C.c_int, [_P, _U8P, C.c_uint32]),
+    "zkfl_debug_ntt_coset": (C.c_int, [_P, _U8P, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int]),
     "zkfl_setup_g1_gen_mul": (C.c_int, [_P, C.c_char_p, C.c_size_t, _U8P]),
     "zkfl_setup_g2_gen_mul": (C.c_int, [_P, C.c_char_p, C.c_size_t, _U8P]),
     "zkfl_setup_g1_scale": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_size_t, _U8P]),
@@ -346,6 +347,18 @@ class Context:
         assert 1 << logn == n
         buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
         check(lib().zkfl_ntt_coset(self.h, buf, logn))
+        return bytes(buf)
+
+    def debug_ntt_coset(self, data: bytes, logn: int, nvec: int = 1, vstride: int | None = None,
+                        col_max: int = -1) -> bytes:
+        """The coset transform of nvec vectors of 2^logn elements in one batched call (parity hook,
+        zkfl_debug_ntt_coset): vector v starts at element v * vstride (default 2^logn); col_max = 0
+        runs the schedule of the domains above 2^20, < 0 the prover's own."""
+        n = 1 << logn
+        vstride = n if vstride is None else vstride
+        assert len(data) == ((nvec - 1) * vstride + n) * 32
+        buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
+        check(lib().zkfl_debug_ntt_coset(self.h, buf, logn, nvec, vstride, col_max))
         return bytes(buf)
 
     def g1_gen_mul(self, scalars: bytes) -> bytes:
