@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "devbufs.h"
 #include "host_parse.h"
 #include "objects.h"
 
@@ -197,32 +198,30 @@ int zkey_load_parsed(zkfl_ctx* ctx, const ZkeyHost& z, size_t len, double parse_
     size_t most = 0;
     for (const Img& o : im) most = std::max(most, o.sidx.size());
     k->msm_c = msm_pick_c(most);
-    std::vector<void*> d_imgs;
-    auto upload = [&](auto& mb, Img& o, bool pairs) -> hipError_t {
-      hipError_t e = msm_bases_alloc(mb, o.sidx.size(), k->msm_c);
-      if (e != hipSuccess || o.sidx.empty()) return e;
-      void* d_img = nullptr;
-      e = hipMalloc(&d_img, o.img.size());
-      if (e != hipSuccess) return e;
-      d_imgs.push_back(d_img);
-      e = hipMemcpyAsync(d_img, o.img.data(), o.img.size(), hipMemcpyHostToDevice, st);
-      if (e == hipSuccess)
-        e = msm_bases_set(mb, static_cast<decltype(mb.bases_w)>(d_img), o.sidx.data(), X, st, pairs);
-      return e;
-    };
     k->a_diff = ab.d_form;
     k->ab_shared = (uint32_t)ab.shared;
-    hipError_t e = upload(k->bA, im[QA], k->a_diff);
-    if (e == hipSuccess) e = upload(k->bB1, im[QB1], false);
-    if (e == hipSuccess) e = upload(k->bB2, im[QB2], false);
     // B_i(tau) G1 and B_i(tau) G2 vanish together in an honest zkey; the sort is shared only when
     // the two index maps really are equal
     k->share_b = im[QB1].sidx == im[QB2].sidx && !im[QB1].sidx.empty();
     k->front = k->share_b && nshards == 1 && logn <= ctx->opts.small_logn;
-    if (e == hipSuccess) e = upload(k->bCH, im[QCH], false);
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-    for (void* d : d_imgs) (void)hipFree(d);
+    hipError_t e;
+    {
+      DevBufs D;  // the images' device copies: freed once the expansions are done
+      auto upload = [&](auto& mb, Img& o, bool pairs) -> hipError_t {
+        ZK_CHECK(msm_bases_alloc(mb, o.sidx.size(), k->msm_c));
+        if (o.sidx.empty()) return hipSuccess;
+        uint8_t* d_img;
+        ZK_CHECK(D.get(&d_img, o.img.size()));
+        ZK_CHECK(hipMemcpyAsync(d_img, o.img.data(), o.img.size(), hipMemcpyHostToDevice, st));
+        return msm_bases_set(mb, reinterpret_cast<decltype(mb.bases_w)>(d_img), o.sidx.data(), X, st, pairs);
+      };
+      e = upload(k->bA, im[QA], k->a_diff);
+      if (e == hipSuccess) e = upload(k->bB1, im[QB1], false);
+      if (e == hipSuccess) e = upload(k->bB2, im[QB2], false);
+      if (e == hipSuccess) e = upload(k->bCH, im[QCH], false);
+      const hipError_t es = hipStreamSynchronize(st);
+      if (e == hipSuccess) e = es;
+    }
     mark("bases_upload");
     if (e != hipSuccess) return cleanup(hip_fail(e, "base expansion"));
   }

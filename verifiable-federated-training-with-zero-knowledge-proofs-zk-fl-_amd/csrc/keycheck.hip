@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devbufs.h"
 #include "host_parse.h"
 #include "objects.h"
 #include "pairing.h"
@@ -216,21 +217,6 @@ __global__ void __launch_bounds__(64) k_key_finish(const G1P* __restrict__ R, co
   store_std(Q, g2_out + p * 32);
 }
 
-// device allocations of one check, freed on every exit path
-struct Dev {
-  std::vector<void*> p;
-  ~Dev() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  template <class T>
-  hipError_t get(T** out, size_t count) {
-    *out = nullptr;
-    const hipError_t e = hipMalloc((void**)out, (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) p.push_back(*out);
-    return e;
-  }
-};
-
 bool nonzero(const uint8_t* p, size_t len) {
   for (size_t i = 0; i < len; i++)
     if (p[i]) return true;
@@ -257,7 +243,7 @@ struct BaseSet {
       sidx.push_back(off + (uint32_t)i);
     }
   }
-  hipError_t upload(Dev& D, hipStream_t st) {
+  hipError_t upload(DevBufs& D, hipStream_t st) {
     ZK_CHECK(D.get(&d_img, n()));
     if (n()) ZK_CHECK(hipMemcpyAsync(d_img, img.data(), img.size(), hipMemcpyHostToDevice, st));
     return hipSuccess;
@@ -369,7 +355,7 @@ extern "C" int zkfl_zkey_check(zkfl_ctx* ctx, const zkfl_r1cs* r1cs, const uint8
 
   HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
   hipStream_t st = ctx->st;
-  Dev D;
+  DevBufs D;
 
   // ---- points ----
   // the header's six points one launch each (a verdict per point: which of gamma2, delta1, delta2

@@ -18,10 +18,12 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "common.h"
+#include "devbufs.h"
 #include "merkle.h"
 #include "poseidon.h"
 #include "zkfl.h"
@@ -311,37 +313,29 @@ int pos_tables_create(PosTables** out, hipStream_t st, std::string& err) {
     total += nc[t] + (size_t)t * t;
   }
   std::vector<uint8_t> raw(total * 32, 0);
-  PosTables* p = new PosTables();
-  Fr* d_raw = nullptr;
-  Fr* d_xy = nullptr;
-  hipError_t e = hipMalloc(&p->buf, total * 32);
-  if (e == hipSuccess) e = hipMalloc(&p->zeros, ZERO_LEVELS * 32);
-  if (e == hipSuccess) e = hipMalloc(&d_raw, total * 32);
-  if (e == hipSuccess) e = hipMalloc(&d_xy, 16 * 2 * 17 * 32);
+  std::unique_ptr<PosTables, void (*)(PosTables*)> p(new PosTables(), pos_tables_free);
+  DevBufs D;
+  Fr *d_raw, *d_xy;
+  const char* const where = "poseidon tables";
+  HIP_TRY_ERR(hipMalloc(&p->buf, total * 32), where, err);
+  HIP_TRY_ERR(hipMalloc(&p->zeros, ZERO_LEVELS * 32), where, err);
+  HIP_TRY_ERR(D.get(&d_raw, total), where, err);
+  HIP_TRY_ERR(D.get(&d_xy, 16 * 2 * 17), where, err);
   std::vector<uint8_t> xy_all(16 * 2 * 17 * 32, 0);
   for (uint32_t t = 2; t <= 17; t++) {
     pos_params_raw(t, raw.data() + 32 * off[t], xy_all.data() + (size_t)(t - 2) * 2 * 17 * 32);
     p->w[t] = {p->buf + off[t], p->buf + off[t] + nc[t], pos_rp(t)};
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(d_raw, raw.data(), raw.size(), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_xy, xy_all.data(), xy_all.size(), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_to_mont, dim3(zk_grid(total, 256)), dim3(256), 0, st, d_raw, total, p->buf);
-    for (uint32_t t = 2; t <= 17; t++)
-      hipLaunchKernelGGL(k_pos_mds, dim3(zk_grid(t * t, 64)), dim3(64), 0, st, d_xy + (size_t)(t - 2) * 2 * 17, t,
-                         p->buf + off[t] + nc[t]);
-    hipLaunchKernelGGL(k_pos_zeros, dim3(1), dim3(64), 0, st, p->w[2], p->w[3], p->zeros, ZERO_LEVELS);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (d_raw) (void)hipFree(d_raw);
-  if (d_xy) (void)hipFree(d_xy);
-  if (e != hipSuccess) {
-    pos_tables_free(p);
-    err = std::string("poseidon tables: ") + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? ZKFL_E_OOM : ZKFL_E_DEVICE;
-  }
-  *out = p;
+  HIP_TRY_ERR(hipMemcpyAsync(d_raw, raw.data(), raw.size(), hipMemcpyHostToDevice, st), where, err);
+  HIP_TRY_ERR(hipMemcpyAsync(d_xy, xy_all.data(), xy_all.size(), hipMemcpyHostToDevice, st), where, err);
+  hipLaunchKernelGGL(k_to_mont, dim3(zk_grid(total, 256)), dim3(256), 0, st, d_raw, total, p->buf);
+  for (uint32_t t = 2; t <= 17; t++)
+    hipLaunchKernelGGL(k_pos_mds, dim3(zk_grid(t * t, 64)), dim3(64), 0, st, d_xy + (size_t)(t - 2) * 2 * 17, t,
+                       p->buf + off[t] + nc[t]);
+  hipLaunchKernelGGL(k_pos_zeros, dim3(1), dim3(64), 0, st, p->w[2], p->w[3], p->zeros, ZERO_LEVELS);
+  HIP_TRY_ERR(hipGetLastError(), where, err);
+  HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
+  *out = p.release();
   return ZKFL_OK;
 }
 

@@ -1,5 +1,6 @@
 // NTT kernels (see ntt.h for the algorithm and the reference behaviour it replaces).
 #include "ntt.h"
+#include "devbufs.h"
 #include "fr_consts.h"
 #include "wtrace.h"
 
@@ -329,18 +330,20 @@ hipError_t ntt_plan_alloc(NttPlan& pl, int logn, hipStream_t st) {
   ZK_CHECK(hipMalloc(&pl.tw_inv, half * sizeof(Fr)));
   ZK_CHECK(hipMalloc(&pl.coset, pl.n * sizeof(Fr)));
   // roots in Montgomery form (converted on device)
-  Fr* tmp;
-  ZK_CHECK(hipMalloc(&tmp, 4 * sizeof(Fr)));
-  uint32_t inc_std[8];
-  for (int i = 0; i < 8; i++) inc_std[i] = (logn == 28) ? FR_SHIFT[i] : FR_ROOT[logn + 1][i];
-  hipLaunchKernelGGL(k_fr_to_mont_one, dim3(1), dim3(1), 0, st, tmp + 0, fr_from_limbs(FR_ROOT[logn]));
-  hipLaunchKernelGGL(k_fr_to_mont_one, dim3(1), dim3(1), 0, st, tmp + 1, fr_from_limbs(FR_ROOT_INV[logn]));
-  hipLaunchKernelGGL(k_fr_to_mont_one, dim3(1), dim3(1), 0, st, tmp + 2, fr_from_limbs(inc_std));
-  hipLaunchKernelGGL(k_fr_to_mont_one, dim3(1), dim3(1), 0, st, tmp + 3, fr_from_limbs(FR_INV_2K[logn]));
   Fr h[4];
-  ZK_CHECK(hipMemcpyAsync(h, tmp, sizeof(h), hipMemcpyDeviceToHost, st));
-  ZK_CHECK(hipStreamSynchronize(st));
-  ZK_CHECK(hipFree(tmp));
+  {
+    DevBufs D;  // tmp goes with this scope, before the tables are filled
+    Fr* tmp;
+    ZK_CHECK(D.get(&tmp, 4));
+    uint32_t inc_std[8];
+    for (int i = 0; i < 8; i++) inc_std[i] = (logn == 28) ? FR_SHIFT[i] : FR_ROOT[logn + 1][i];
+    hipLaunchKernelGGL(k_fr_to_mont_one, dim3(1), dim3(1), 0, st, tmp + 0, fr_from_limbs(FR_ROOT[logn]));
+    hipLaunchKernelGGL(k_fr_to_mont_one, dim3(1), dim3(1), 0, st, tmp + 1, fr_from_limbs(FR_ROOT_INV[logn]));
+    hipLaunchKernelGGL(k_fr_to_mont_one, dim3(1), dim3(1), 0, st, tmp + 2, fr_from_limbs(inc_std));
+    hipLaunchKernelGGL(k_fr_to_mont_one, dim3(1), dim3(1), 0, st, tmp + 3, fr_from_limbs(FR_INV_2K[logn]));
+    ZK_CHECK(hipMemcpyAsync(h, tmp, sizeof(h), hipMemcpyDeviceToHost, st));
+    ZK_CHECK(hipStreamSynchronize(st));
+  }
   hipLaunchKernelGGL(k_ntt_twiddles, dim3(zk_grid(half, 256)), dim3(256), 0, st, pl.tw_fwd, half, h[0]);
   hipLaunchKernelGGL(k_ntt_twiddles, dim3(zk_grid(half, 256)), dim3(256), 0, st, pl.tw_inv, half, h[1]);
   hipLaunchKernelGGL(k_ntt_coset_table, dim3(zk_grid(pl.n, 256)), dim3(256), 0, st, pl.coset, pl.n,

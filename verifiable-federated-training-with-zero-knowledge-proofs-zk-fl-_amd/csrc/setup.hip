@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "curve.h"
+#include "devbufs.h"
 #include "fr_consts.h"
 #include "ntt.h"
 
@@ -108,30 +109,15 @@ __global__ void __launch_bounds__(64) k_gfft_out(const XYZZ<F>* __restrict__ x, 
   out[j] = xyzz_to_affine<F>(smul_xyzz<F>(x[src], ninv.v));
 }
 
-struct DevBufs {
-  std::vector<void*> p;
-  template <class T>
-  hipError_t alloc(T** out, size_t bytes) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes ? bytes : 1);
-    if (e == hipSuccess) p.push_back(q);
-    *out = static_cast<T*>(q);
-    return e;
-  }
-  ~DevBufs() {
-    for (void* q : p) (void)hipFree(q);
-  }
-};
-
 template <class F>
 hipError_t scale_t(hipStream_t st, const uint8_t* points, const uint8_t* scalars, size_t n, uint8_t* out) {
   if (n == 0) return hipSuccess;
   DevBufs b;
   Affine<F>*d_p, *d_o;
   uint32_t* d_s;
-  ZK_CHECK(b.alloc(&d_p, n * sizeof(Affine<F>)));
-  ZK_CHECK(b.alloc(&d_o, n * sizeof(Affine<F>)));
-  ZK_CHECK(b.alloc(&d_s, n * 32));
+  ZK_CHECK(b.get(&d_p, n));
+  ZK_CHECK(b.get(&d_o, n));
+  ZK_CHECK(b.get(&d_s, n * 8));
   ZK_CHECK(hipMemcpyAsync(d_p, points, n * sizeof(Affine<F>), hipMemcpyHostToDevice, st));
   ZK_CHECK(hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_scale<F>, dim3(zk_grid(n, 64)), dim3(64), 0, st, d_p, d_s, n, d_o);
@@ -146,11 +132,11 @@ hipError_t lagrange_t(hipStream_t st, const uint8_t* points, int logn, uint8_t* 
   DevBufs b;
   Affine<F>* d_a;
   XYZZ<F>* d_x;
-  ZK_CHECK(b.alloc(&d_a, n * sizeof(Affine<F>)));
-  ZK_CHECK(b.alloc(&d_x, n * sizeof(XYZZ<F>)));
-  NttPlan pl;
-  ZK_CHECK(ntt_plan_alloc(pl, logn, st));  // tw_inv[m] = w^-m, m < n/2
-  hipError_t e = hipMemcpyAsync(d_a, points, n * sizeof(Affine<F>), hipMemcpyHostToDevice, st);
+  ZK_CHECK(b.get(&d_a, n));
+  ZK_CHECK(b.get(&d_x, n));
+  NttPlan pl;  // freed below: one way out from here on
+  hipError_t e = ntt_plan_alloc(pl, logn, st);  // tw_inv[m] = w^-m, m < n/2
+  if (e == hipSuccess) e = hipMemcpyAsync(d_a, points, n * sizeof(Affine<F>), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_to_xyzz<F>, dim3(zk_grid(n, 64)), dim3(64), 0, st, d_a, n, d_x);
     for (int s = logn - 1; s >= 0; s--) {
@@ -198,10 +184,10 @@ hipError_t lincomb_t(hipStream_t st, const uint8_t* bases, size_t n_bases, size_
   DevBufs b;
   Affine<F>*d_b, *d_o;
   uint32_t *d_i, *d_c;
-  ZK_CHECK(b.alloc(&d_b, n_bases * sizeof(Affine<F>)));
-  ZK_CHECK(b.alloc(&d_o, n_out * sizeof(Affine<F>)));
-  ZK_CHECK(b.alloc(&d_i, nnz * 4));
-  ZK_CHECK(b.alloc(&d_c, nnz * 32));
+  ZK_CHECK(b.get(&d_b, n_bases));
+  ZK_CHECK(b.get(&d_o, n_out));
+  ZK_CHECK(b.get(&d_i, nnz));
+  ZK_CHECK(b.get(&d_c, nnz * 8));
   if (n_bases) ZK_CHECK(hipMemcpyAsync(d_b, bases, n_bases * sizeof(Affine<F>), hipMemcpyHostToDevice, st));
   if (nnz) {
     ZK_CHECK(hipMemcpyAsync(d_i, idx, nnz * 4, hipMemcpyHostToDevice, st));
@@ -216,9 +202,9 @@ hipError_t lincomb_t(hipStream_t st, const uint8_t* bases, size_t n_bases, size_
     const size_t nch = cs.size() - 1;
     uint32_t *d_cs, *d_crp;
     XYZZ<F>* part;
-    ZK_CHECK(b.alloc(&d_cs, cs.size() * 4));
-    ZK_CHECK(b.alloc(&d_crp, crp.size() * 4));
-    ZK_CHECK(b.alloc(&part, nch * sizeof(XYZZ<F>)));
+    ZK_CHECK(b.get(&d_cs, cs.size()));
+    ZK_CHECK(b.get(&d_crp, crp.size()));
+    ZK_CHECK(b.get(&part, nch));
     ZK_CHECK(hipMemcpyAsync(d_cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, st));
     ZK_CHECK(hipMemcpyAsync(d_crp, crp.data(), crp.size() * 4, hipMemcpyHostToDevice, st));
     if (nch) {
@@ -290,9 +276,9 @@ hipError_t gen_mul_t(hipStream_t st, const uint8_t* scalars, size_t n, uint8_t* 
   DevBufs b;
   uint32_t* d_s;
   Affine<F>*d_o, *d_g;
-  ZK_CHECK(b.alloc(&d_s, n * 32));
-  ZK_CHECK(b.alloc(&d_o, n * sizeof(Affine<F>)));
-  ZK_CHECK(b.alloc(&d_g, sizeof(Affine<F>)));
+  ZK_CHECK(b.get(&d_s, n * 8));
+  ZK_CHECK(b.get(&d_o, n));
+  ZK_CHECK(b.get(&d_g, 1));
   ZK_CHECK(hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st));
   if constexpr (std::is_same<F, Fq2Ops>::value)
     hipLaunchKernelGGL(k_g2_gen_mont, dim3(1), dim3(1), 0, st, d_g);

@@ -17,9 +17,11 @@
 #include <string.h>
 
 #include <cstdio>
+#include <memory>
 
 #include "common.h"
 #include "curve.h"
+#include "devbufs.h"
 #include "pairing.h"
 #include "verify.h"
 #include "verify_dev.h"
@@ -178,15 +180,7 @@ __global__ void k_fq12_to_std(size_t n, const Fq12* in, uint32_t* out) {
   }
 }
 
-int hip_err(hipError_t e, const char* where, std::string& err) {
-  err = std::string(where) + ": " + hipGetErrorString(e);
-  return e == hipErrorOutOfMemory ? ZKFL_E_OOM : ZKFL_E_DEVICE;
-}
-
-template <class T>
-hipError_t dalloc(T** p, size_t count) {
-  return hipMalloc((void**)p, count * sizeof(T) + 16);
-}
+constexpr size_t PAD = 16;  // bytes behind every allocation of this unit
 
 }  // namespace
 
@@ -214,56 +208,45 @@ int vk_prepare(const uint8_t* vkb, size_t len, hipStream_t st, VkDev** out, std:
     err = "verification key: length does not match nPublic";
     return ZKFL_E_FORMAT;
   }
-  VkDev* vk = new VkDev();
+  std::unique_ptr<VkDev, void (*)(VkDev*)> vk(new VkDev(), vk_free);
   vk->bytes.assign(vkb, vkb + len);
   vk->npub = npub;
-  uint32_t* d_in = nullptr;   // the vk image without the count (u32 aligned)
-  uint32_t* d_stat = nullptr; // [npub+1 IC | 3 G2 | 1 alpha]
-  int rc = ZKFL_OK;
+  DevBufs D;
+  uint32_t* d_in;    // the vk image without the count (u32 aligned)
+  uint32_t* d_stat;  // [npub+1 IC | 3 G2 | 1 alpha]
   const size_t nwords = (len - 4) / 4;
-  hipError_t e = dalloc(&d_in, nwords);
-  if (e == hipSuccess) e = dalloc(&d_stat, npub + 5);
-  if (e == hipSuccess) e = dalloc(&vk->ic_table, (size_t)(npub + 1) * 16);
-  if (e == hipSuccess) e = dalloc(&vk->lines, 3 * (size_t)ATE_NLINES);
-  if (e == hipSuccess) e = dalloc(&vk->f_ab, 1);
-  if (e == hipSuccess) e = dalloc(&vk->alpha, 1);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_in, vkb + 4, len - 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_stat, 0, (npub + 5) * 4, st);
-  if (e == hipSuccess) {
-    // layout (u32 words): alpha1 [0,16) beta2 [16,48) gamma2 [48,80) delta2 [80,112) IC [112, ...)
-    hipLaunchKernelGGL(k_ic_tables, dim3(zk_grid(npub + 1, 64)), dim3(64), 0, st, npub + 1, d_in + 112,
-                       vk->ic_table, d_stat);
-    hipLaunchKernelGGL(k_g2_prepare, dim3(1), dim3(64), 0, st, (size_t)3, d_in + 16, (size_t)32, 1, vk->lines,
-                       d_stat + npub + 1);
-    hipLaunchKernelGGL(k_g1_load, dim3(1), dim3(64), 0, st, (size_t)1, d_in, vk->alpha, d_stat + npub + 4);
-    PairLines L = {};
-    L.base[0] = vk->lines;  // beta2
-    hipLaunchKernelGGL(k_miller, dim3(1), dim3(64), 0, st, (size_t)1, 1, (const G1Aff*)vk->alpha, L,
-                       (const Fq12*)nullptr, (const uint32_t*)nullptr, 0, vk->f_ab, (int32_t*)nullptr);
-    e = hipGetLastError();
-  }
+  const char* const where = "vk_prepare";
+  HIP_TRY_ERR(D.get(&d_in, nwords, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_stat, npub + 5, PAD), where, err);
+  // the key's own tables: vk_free's
+  HIP_TRY_ERR(hipMalloc(&vk->ic_table, (size_t)(npub + 1) * 16 * sizeof(G1Aff) + PAD), where, err);
+  HIP_TRY_ERR(hipMalloc(&vk->lines, 3 * (size_t)ATE_NLINES * sizeof(LineCoef) + PAD), where, err);
+  HIP_TRY_ERR(hipMalloc(&vk->f_ab, sizeof(Fq12) + PAD), where, err);
+  HIP_TRY_ERR(hipMalloc(&vk->alpha, sizeof(G1Aff) + PAD), where, err);
+  HIP_TRY_ERR(hipMemcpyAsync(d_in, vkb + 4, len - 4, hipMemcpyHostToDevice, st), where, err);
+  HIP_TRY_ERR(hipMemsetAsync(d_stat, 0, (npub + 5) * 4, st), where, err);
+  // layout (u32 words): alpha1 [0,16) beta2 [16,48) gamma2 [48,80) delta2 [80,112) IC [112, ...)
+  hipLaunchKernelGGL(k_ic_tables, dim3(zk_grid(npub + 1, 64)), dim3(64), 0, st, npub + 1, d_in + 112, vk->ic_table,
+                     d_stat);
+  hipLaunchKernelGGL(k_g2_prepare, dim3(1), dim3(64), 0, st, (size_t)3, d_in + 16, (size_t)32, 1, vk->lines,
+                     d_stat + npub + 1);
+  hipLaunchKernelGGL(k_g1_load, dim3(1), dim3(64), 0, st, (size_t)1, d_in, vk->alpha, d_stat + npub + 4);
+  PairLines L = {};
+  L.base[0] = vk->lines;  // beta2
+  hipLaunchKernelGGL(k_miller, dim3(1), dim3(64), 0, st, (size_t)1, 1, (const G1Aff*)vk->alpha, L,
+                     (const Fq12*)nullptr, (const uint32_t*)nullptr, 0, vk->f_ab, (int32_t*)nullptr);
+  HIP_TRY_ERR(hipGetLastError(), where, err);
   std::vector<uint32_t> stat(npub + 5);
-  if (e == hipSuccess) e = hipMemcpyAsync(stat.data(), d_stat, (npub + 5) * 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    rc = hip_err(e, "vk_prepare", err);
-  } else {
-    for (uint32_t i = 0; i < npub + 5 && rc == ZKFL_OK; i++) {
-      // IC entries may be infinity; alpha/beta/gamma/delta must be proper points
-      bool bad = (stat[i] & ST_BAD) || (i > npub && stat[i] != 0);
-      if (bad) {
-        err = "verification key: point off curve / not in subgroup / at infinity";
-        rc = ZKFL_E_FORMAT;
-      }
+  HIP_TRY_ERR(hipMemcpyAsync(stat.data(), d_stat, (npub + 5) * 4, hipMemcpyDeviceToHost, st), where, err);
+  HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
+  for (uint32_t i = 0; i < npub + 5; i++) {
+    // IC entries may be infinity; alpha/beta/gamma/delta must be proper points
+    if ((stat[i] & ST_BAD) || (i > npub && stat[i] != 0)) {
+      err = "verification key: point off curve / not in subgroup / at infinity";
+      return ZKFL_E_FORMAT;
     }
   }
-  if (d_in) (void)hipFree(d_in);
-  if (d_stat) (void)hipFree(d_stat);
-  if (rc != ZKFL_OK) {
-    vk_free(vk);
-    return rc;
-  }
-  *out = vk;
+  *out = vk.release();
   return ZKFL_OK;
 }
 
@@ -273,22 +256,24 @@ int verify_batch(const VkDev* vk, size_t n, const uint8_t* pubs, const uint8_t* 
   const size_t CH = 4096;  // proofs per chunk: 4096 x 102 lines x 192 B = 80 MB of lines
   const size_t cap = n < CH ? n : CH;
   const uint32_t npub = vk->npub;
-  uint32_t *d_pub = nullptr, *d_proof = nullptr, *d_bstat = nullptr, *d_status = nullptr;
-  LineCoef* d_lines = nullptr;
-  G1Aff* d_P = nullptr;
-  int32_t* d_res = nullptr;
-  hipError_t e = dalloc(&d_pub, cap * npub * 8);
-  if (e == hipSuccess) e = dalloc(&d_proof, cap * 64);
-  if (e == hipSuccess) e = dalloc(&d_bstat, cap);
-  if (e == hipSuccess) e = dalloc(&d_status, cap);
-  if (e == hipSuccess) e = dalloc(&d_lines, cap * ATE_NLINES);
-  if (e == hipSuccess) e = dalloc(&d_P, cap * 3);
-  if (e == hipSuccess) e = dalloc(&d_res, cap);
-  for (size_t off = 0; off < n && e == hipSuccess; off += cap) {
-    size_t m = (n - off < cap) ? n - off : cap;
-    if (npub) e = hipMemcpyAsync(d_pub, pubs + off * npub * 32, m * npub * 32, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_proof, proofs + off * 256, m * 256, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) break;
+  DevBufs D;
+  uint32_t *d_pub, *d_proof, *d_bstat, *d_status;
+  LineCoef* d_lines;
+  G1Aff* d_P;
+  int32_t* d_res;
+  const char* const where = "verify_batch";
+  HIP_TRY_ERR(D.get(&d_pub, cap * npub * 8, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_proof, cap * 64, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_bstat, cap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_status, cap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_lines, cap * ATE_NLINES, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_P, cap * 3, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_res, cap, PAD), where, err);
+  for (size_t off = 0; off < n; off += cap) {
+    const size_t m = (n - off < cap) ? n - off : cap;
+    if (npub)
+      HIP_TRY_ERR(hipMemcpyAsync(d_pub, pubs + off * npub * 32, m * npub * 32, hipMemcpyHostToDevice, st), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(d_proof, proofs + off * 256, m * 256, hipMemcpyHostToDevice, st), where, err);
     unsigned g = zk_grid(m, 64);
     hipLaunchKernelGGL(k_g2_prepare, dim3(g), dim3(64), 0, st, m, d_proof + 16, (size_t)64, 1, d_lines, d_bstat);
     hipLaunchKernelGGL(k_verify_inputs, dim3(g), dim3(64), 0, st, m, npub, d_pub, d_proof,
@@ -300,71 +285,50 @@ int verify_batch(const VkDev* vk, size_t n, const uint8_t* pubs, const uint8_t* 
     L.base[2] = vk->lines + 2 * ATE_NLINES;  // delta2
     hipLaunchKernelGGL(k_miller, dim3(g), dim3(64), 0, st, m, 3, (const G1Aff*)d_P, L, (const Fq12*)vk->f_ab,
                        (const uint32_t*)d_status, 1, (Fq12*)nullptr, d_res);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(results + off, d_res, m * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    HIP_TRY_ERR(hipGetLastError(), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(results + off, d_res, m * 4, hipMemcpyDeviceToHost, st), where, err);
+    HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
   }
-  int rc = (e == hipSuccess) ? ZKFL_OK : hip_err(e, "verify_batch", err);
-  for (void* p : {(void*)d_pub, (void*)d_proof, (void*)d_bstat, (void*)d_status, (void*)d_lines, (void*)d_P,
-                  (void*)d_res})
-    if (p) (void)hipFree(p);
-  return rc;
+  return ZKFL_OK;
 }
 
 int pairing_batch(size_t n, const uint8_t* g1, const uint8_t* g2, int final_exp, uint8_t* out, hipStream_t st,
                   std::string& err) {
   if (n == 0) return ZKFL_OK;
-  uint32_t *d_g1 = nullptr, *d_g2 = nullptr, *d_stat = nullptr, *d_out = nullptr;
-  LineCoef* d_lines = nullptr;
-  G1Aff* d_P = nullptr;
-  Fq12* d_f = nullptr;
-  hipError_t e = dalloc(&d_g1, n * 16);
-  if (e == hipSuccess) e = dalloc(&d_g2, n * 32);
-  if (e == hipSuccess) e = dalloc(&d_stat, 2 * n);
-  if (e == hipSuccess) e = dalloc(&d_lines, n * ATE_NLINES);
-  if (e == hipSuccess) e = dalloc(&d_P, n);
-  if (e == hipSuccess) e = dalloc(&d_f, n);
-  if (e == hipSuccess) e = dalloc(&d_out, n * 96);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_g1, g1, n * 64, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_g2, g2, n * 128, hipMemcpyHostToDevice, st);
+  DevBufs D;
+  uint32_t *d_g1, *d_g2, *d_stat, *d_out;
+  LineCoef* d_lines;
+  G1Aff* d_P;
+  Fq12* d_f;
+  const char* const where = "pairing_batch";
+  HIP_TRY_ERR(D.get(&d_g1, n * 16, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_g2, n * 32, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_stat, 2 * n, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_lines, n * ATE_NLINES, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_P, n, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_f, n, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_out, n * 96, PAD), where, err);
+  HIP_TRY_ERR(hipMemcpyAsync(d_g1, g1, n * 64, hipMemcpyHostToDevice, st), where, err);
+  HIP_TRY_ERR(hipMemcpyAsync(d_g2, g2, n * 128, hipMemcpyHostToDevice, st), where, err);
   std::vector<uint32_t> stat(2 * n);
-  if (e == hipSuccess) {
-    unsigned g = zk_grid(n, 64);
-    hipLaunchKernelGGL(k_g1_load, dim3(g), dim3(64), 0, st, n, d_g1, d_P, d_stat);
-    hipLaunchKernelGGL(k_g2_prepare, dim3(g), dim3(64), 0, st, n, d_g2, (size_t)32, 1, d_lines, d_stat + n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(stat.data(), d_stat, 2 * n * 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  int rc = ZKFL_OK;
-  if (e == hipSuccess) {
-    for (size_t i = 0; i < 2 * n; i++)
-      if (stat[i] & ST_BAD) {
-        err = "pairing: point " + std::to_string(i % n) + (i < n ? " (G1)" : " (G2)") +
-              " is not canonical / not on the curve / not in the subgroup";
-        rc = ZKFL_E_ARG;
-        break;
-      }
-    // a G2 point at infinity: mark the G1 side as infinity so the pair contributes 1
-    for (size_t i = 0; i < n && rc == ZKFL_OK; i++)
-      if (stat[n + i] == ST_INF) e = hipMemsetAsync(d_P + i, 0, sizeof(G1Aff), st);
-  }
-  if (rc == ZKFL_OK && e == hipSuccess) {
-    unsigned g = zk_grid(n, 64);
-    PairLines L = {};
-    L.base[0] = d_lines;
-    L.stride[0] = ATE_NLINES;
-    hipLaunchKernelGGL(k_miller, dim3(g), dim3(64), 0, st, n, 1, (const G1Aff*)d_P, L, (const Fq12*)nullptr,
-                       (const uint32_t*)nullptr, final_exp, d_f, (int32_t*)nullptr);
-    hipLaunchKernelGGL(k_fq12_to_std, dim3(g), dim3(64), 0, st, n, (const Fq12*)d_f, d_out);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * 384, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  if (rc == ZKFL_OK && e != hipSuccess) rc = hip_err(e, "pairing_batch", err);
-  for (void* p : {(void*)d_g1, (void*)d_g2, (void*)d_stat, (void*)d_lines, (void*)d_P, (void*)d_f, (void*)d_out})
-    if (p) (void)hipFree(p);
-  return rc;
+  const unsigned g = zk_grid(n, 64);
+  hipLaunchKernelGGL(k_g1_load, dim3(g), dim3(64), 0, st, n, d_g1, d_P, d_stat);
+  hipLaunchKernelGGL(k_g2_prepare, dim3(g), dim3(64), 0, st, n, d_g2, (size_t)32, 1, d_lines, d_stat + n);
+  HIP_TRY_ERR(hipGetLastError(), where, err);
+  HIP_TRY_ERR(hipMemcpyAsync(stat.data(), d_stat, 2 * n * 4, hipMemcpyDeviceToHost, st), where, err);
+  HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
+  if (const int rc = pairing_points_check(stat, n, err)) return rc;
+  HIP_TRY_ERR(pairing_fix_infinity(stat, n, d_P, st), where, err);
+  PairLines L = {};
+  L.base[0] = d_lines;
+  L.stride[0] = ATE_NLINES;
+  hipLaunchKernelGGL(k_miller, dim3(g), dim3(64), 0, st, n, 1, (const G1Aff*)d_P, L, (const Fq12*)nullptr,
+                     (const uint32_t*)nullptr, final_exp, d_f, (int32_t*)nullptr);
+  hipLaunchKernelGGL(k_fq12_to_std, dim3(g), dim3(64), 0, st, n, (const Fq12*)d_f, d_out);
+  HIP_TRY_ERR(hipGetLastError(), where, err);
+  HIP_TRY_ERR(hipMemcpyAsync(out, d_out, n * 384, hipMemcpyDeviceToHost, st), where, err);
+  HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
+  return ZKFL_OK;
 }
 
 }  // namespace zkfl

@@ -5,10 +5,12 @@
 #pragma once
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
 #include "curve.h"
 #include "pairing.h"
+#include "zkfl.h"
 
 namespace zkfl {
 
@@ -24,6 +26,28 @@ struct VkDev {
 };
 
 constexpr uint32_t ST_INF = 1u, ST_BAD = 2u;
+
+// Host side of the two pairing hooks.  stat: the decode statuses of n G1 points, then of their n G2
+// points.  The first point that is not a proper one is named in err (ZKFL_E_ARG).
+inline int pairing_points_check(const std::vector<uint32_t>& stat, size_t n, std::string& err) {
+  for (size_t i = 0; i < 2 * n; i++)
+    if (stat[i] & ST_BAD) {
+      err = "pairing: point " + std::to_string(i % n) + (i < n ? " (G1)" : " (G2)") +
+            " is not canonical / not on the curve / not in the subgroup";
+      return ZKFL_E_ARG;
+    }
+  return ZKFL_OK;
+}
+
+// A G2 point at infinity: its G1 side (d_P[i]) is made infinity too, so the pair contributes 1.
+inline hipError_t pairing_fix_infinity(const std::vector<uint32_t>& stat, size_t n, G1Aff* d_P, hipStream_t st) {
+  for (size_t i = 0; i < n; i++)
+    if (stat[n + i] == ST_INF) {
+      const hipError_t e = hipMemsetAsync(d_P + i, 0, sizeof(G1Aff), st);
+      if (e != hipSuccess) return e;
+    }
+  return hipSuccess;
+}
 
 ZK_DEV bool lt_mod(const uint32_t* v, const uint32_t* P) {
   for (int i = 7; i >= 0; i--)

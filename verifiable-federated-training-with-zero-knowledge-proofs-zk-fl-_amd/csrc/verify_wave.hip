@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "curve.h"
+#include "devbufs.h"
 #include "pairing_wave.h"
 #include "verify.h"
 #include "verify_dev.h"
@@ -213,15 +214,7 @@ __global__ __launch_bounds__(64) void k_wave_miller(int npairs, const G1Aff* P, 
   if (result && threadIdx.x == 0) result[k] = wv_is_one(&s, 0) ? 1 : 0;
 }
 
-int hip_err(hipError_t e, const char* where, std::string& err) {
-  err = std::string(where) + ": " + hipGetErrorString(e);
-  return e == hipErrorOutOfMemory ? ZKFL_E_OOM : ZKFL_E_DEVICE;
-}
-
-template <class T>
-hipError_t dalloc(T** p, size_t count) {
-  return hipMalloc((void**)p, count * sizeof(T) + 16);
-}
+constexpr size_t PAD = 16;  // bytes behind every allocation of this unit
 
 }  // namespace
 
@@ -229,24 +222,18 @@ int vk_wave_tables(const VkDev* vk, hipStream_t st, void** out, std::string& err
   *out = nullptr;
   const uint32_t npub = vk->npub;
   if (npub == 0 || npub > ZKFL_VERIFY_WAVE_MAX_PUBLIC) return ZKFL_OK;
-  uint32_t* d_ic = nullptr;
-  G1Aff* tab = nullptr;
+  DevBufs D;
+  uint32_t* d_ic;
+  G1Aff* tab;
   const size_t ic_bytes = 64ull * (npub + 1);
-  hipError_t e = dalloc(&d_ic, ic_bytes / 4);
-  if (e == hipSuccess) e = dalloc(&tab, (size_t)npub * 64 * 16);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_ic, vk->bytes.data() + 4 + 448, ic_bytes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_wave_ic_tables, dim3(npub), dim3(64), 0, st, npub, (const uint32_t*)d_ic, tab);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (d_ic) (void)hipFree(d_ic);
-  if (e != hipSuccess) {
-    if (tab) (void)hipFree(tab);
-    return hip_err(e, "vk_wave_tables", err);
-  }
-  *out = tab;
+  const char* const where = "vk_wave_tables";
+  HIP_TRY_ERR(D.get(&d_ic, ic_bytes / 4, PAD), where, err);
+  HIP_TRY_ERR(D.get(&tab, (size_t)npub * 64 * 16, PAD), where, err);
+  HIP_TRY_ERR(hipMemcpyAsync(d_ic, vk->bytes.data() + 4 + 448, ic_bytes, hipMemcpyHostToDevice, st), where, err);
+  hipLaunchKernelGGL(k_wave_ic_tables, dim3(npub), dim3(64), 0, st, npub, (const uint32_t*)d_ic, tab);
+  HIP_TRY_ERR(hipGetLastError(), where, err);
+  HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
+  *out = D.keep(tab);  // vk_wave_tables_free's from here on
   return ZKFL_OK;
 }
 
@@ -275,28 +262,29 @@ int verify_wave(size_t n, const VerifyJob* jobs, const uint8_t* proofs, int32_t*
     }
     if (words > max_pub) max_pub = words;
   }
-  WaveJob* d_jobs = nullptr;
-  uint32_t *d_pub = nullptr, *d_proof = nullptr, *d_bstat = nullptr, *d_status = nullptr;
-  LineCoef* d_lines = nullptr;
-  G1Aff* d_P = nullptr;
-  int32_t* d_res = nullptr;
-  hipError_t e = dalloc(&d_jobs, cap);
-  if (e == hipSuccess) e = dalloc(&d_pub, max_pub * 8);
-  if (e == hipSuccess) e = dalloc(&d_proof, cap * 64);
-  if (e == hipSuccess) e = dalloc(&d_bstat, cap);
-  if (e == hipSuccess) e = dalloc(&d_status, cap);
-  if (e == hipSuccess) e = dalloc(&d_lines, cap * ATE_NLINES);
-  if (e == hipSuccess) e = dalloc(&d_P, cap * 3);
-  if (e == hipSuccess) e = dalloc(&d_res, cap);
-  for (size_t off = 0; off < n && e == hipSuccess; off += cap) {
+  DevBufs D;
+  WaveJob* d_jobs;
+  uint32_t *d_pub, *d_proof, *d_bstat, *d_status;
+  LineCoef* d_lines;
+  G1Aff* d_P;
+  int32_t* d_res;
+  const char* const where = "verify_wave";
+  HIP_TRY_ERR(D.get(&d_jobs, cap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_pub, max_pub * 8, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_proof, cap * 64, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_bstat, cap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_status, cap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_lines, cap * ATE_NLINES, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_P, cap * 3, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_res, cap, PAD), where, err);
+  for (size_t off = 0; off < n; off += cap) {
     const size_t m = (n - off < cap) ? n - off : cap;
     hpub.clear();
     for (size_t i = off; i < off + m; i++) hpub.insert(hpub.end(), jobs[i].pub, jobs[i].pub + 32ull * hj[i].npub);
-    e = hipMemcpyAsync(d_jobs, hj.data() + off, m * sizeof(WaveJob), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && !hpub.empty())
-      e = hipMemcpyAsync(d_pub, hpub.data(), hpub.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_proof, proofs + off * 256, m * 256, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) break;
+    HIP_TRY_ERR(hipMemcpyAsync(d_jobs, hj.data() + off, m * sizeof(WaveJob), hipMemcpyHostToDevice, st), where, err);
+    if (!hpub.empty())
+      HIP_TRY_ERR(hipMemcpyAsync(d_pub, hpub.data(), hpub.size(), hipMemcpyHostToDevice, st), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(d_proof, proofs + off * 256, m * 256, hipMemcpyHostToDevice, st), where, err);
     const dim3 g((unsigned)m), b(64);
     int pi = prof ? prof->begin("verify_wave_g2", st) : -1;
     hipLaunchKernelGGL(k_wave_g2_prepare, dim3(2 * g.x), b, 0, st, (const uint32_t*)(d_proof + 16), (size_t)64, d_lines, d_bstat,
@@ -310,68 +298,48 @@ int verify_wave(size_t n, const VerifyJob* jobs, const uint8_t* proofs, int32_t*
     hipLaunchKernelGGL(k_wave_miller, g, b, 0, st, 3, (const G1Aff*)d_P, (const LineCoef*)d_lines,
                        (const WaveJob*)d_jobs, (const uint32_t*)d_status, 1, (uint32_t*)nullptr, d_res);
     if (prof) prof->end(pi, st, (double)m);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(results + off, d_res, m * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);  // hpub is reused by the next chunk
+    HIP_TRY_ERR(hipGetLastError(), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(results + off, d_res, m * 4, hipMemcpyDeviceToHost, st), where, err);
+    HIP_TRY_ERR(hipStreamSynchronize(st), where, err);  // hpub is reused by the next chunk
   }
-  int rc = (e == hipSuccess) ? ZKFL_OK : hip_err(e, "verify_wave", err);
-  for (void* p : {(void*)d_jobs, (void*)d_pub, (void*)d_proof, (void*)d_bstat, (void*)d_status, (void*)d_lines,
-                  (void*)d_P, (void*)d_res})
-    if (p) (void)hipFree(p);
-  return rc;
+  return ZKFL_OK;
 }
 
 int pairing_wave_batch(size_t n, const uint8_t* g1, const uint8_t* g2, int final_exp, uint8_t* out, hipStream_t st,
                        Profiler* prof, std::string& err) {
   if (n == 0) return ZKFL_OK;
-  uint32_t *d_g1 = nullptr, *d_g2 = nullptr, *d_stat = nullptr, *d_out = nullptr;
-  LineCoef* d_lines = nullptr;
-  G1Aff* d_P = nullptr;
-  hipError_t e = dalloc(&d_g1, n * 16);
-  if (e == hipSuccess) e = dalloc(&d_g2, n * 32);
-  if (e == hipSuccess) e = dalloc(&d_stat, 2 * n);
-  if (e == hipSuccess) e = dalloc(&d_lines, n * ATE_NLINES);
-  if (e == hipSuccess) e = dalloc(&d_P, n);
-  if (e == hipSuccess) e = dalloc(&d_out, n * 96);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_g1, g1, n * 64, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_g2, g2, n * 128, hipMemcpyHostToDevice, st);
+  DevBufs D;
+  uint32_t *d_g1, *d_g2, *d_stat, *d_out;
+  LineCoef* d_lines;
+  G1Aff* d_P;
+  const char* const where = "pairing_wave_batch";
+  HIP_TRY_ERR(D.get(&d_g1, n * 16, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_g2, n * 32, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_stat, 2 * n, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_lines, n * ATE_NLINES, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_P, n, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_out, n * 96, PAD), where, err);
+  HIP_TRY_ERR(hipMemcpyAsync(d_g1, g1, n * 64, hipMemcpyHostToDevice, st), where, err);
+  HIP_TRY_ERR(hipMemcpyAsync(d_g2, g2, n * 128, hipMemcpyHostToDevice, st), where, err);
   std::vector<uint32_t> stat(2 * n);
   const dim3 g((unsigned)n), b(64);
-  if (e == hipSuccess) {
-    int pi = prof ? prof->begin("verify_wave_g2", st) : -1;
-    hipLaunchKernelGGL(k_wave_g2_prepare, dim3(2 * g.x), b, 0, st, (const uint32_t*)d_g2, (size_t)32, d_lines, d_stat + n,
-                       (const uint32_t*)d_g1, d_P, d_stat);
-    if (prof) prof->end(pi, st, (double)n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(stat.data(), d_stat, 2 * n * 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  int rc = ZKFL_OK;
-  if (e == hipSuccess) {
-    for (size_t i = 0; i < 2 * n; i++)
-      if (stat[i] & ST_BAD) {
-        err = "pairing: point " + std::to_string(i % n) + (i < n ? " (G1)" : " (G2)") +
-              " is not canonical / not on the curve / not in the subgroup";
-        rc = ZKFL_E_ARG;
-        break;
-      }
-    // a G2 point at infinity: mark the G1 side as infinity so the pair contributes 1
-    for (size_t i = 0; i < n && rc == ZKFL_OK && e == hipSuccess; i++)
-      if (stat[n + i] == ST_INF) e = hipMemsetAsync(d_P + i, 0, sizeof(G1Aff), st);
-  }
-  if (rc == ZKFL_OK && e == hipSuccess) {
-    int pi = prof ? prof->begin("verify_wave_pair", st) : -1;
-    hipLaunchKernelGGL(k_wave_miller, g, b, 0, st, 1, (const G1Aff*)d_P, (const LineCoef*)d_lines,
-                       (const WaveJob*)nullptr, (const uint32_t*)nullptr, final_exp, d_out, (int32_t*)nullptr);
-    if (prof) prof->end(pi, st, (double)n);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * 384, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  if (rc == ZKFL_OK && e != hipSuccess) rc = hip_err(e, "pairing_wave_batch", err);
-  for (void* p : {(void*)d_g1, (void*)d_g2, (void*)d_stat, (void*)d_lines, (void*)d_P, (void*)d_out})
-    if (p) (void)hipFree(p);
-  return rc;
+  int pi = prof ? prof->begin("verify_wave_g2", st) : -1;
+  hipLaunchKernelGGL(k_wave_g2_prepare, dim3(2 * g.x), b, 0, st, (const uint32_t*)d_g2, (size_t)32, d_lines, d_stat + n,
+                     (const uint32_t*)d_g1, d_P, d_stat);
+  if (prof) prof->end(pi, st, (double)n);
+  HIP_TRY_ERR(hipGetLastError(), where, err);
+  HIP_TRY_ERR(hipMemcpyAsync(stat.data(), d_stat, 2 * n * 4, hipMemcpyDeviceToHost, st), where, err);
+  HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
+  if (const int rc = pairing_points_check(stat, n, err)) return rc;
+  HIP_TRY_ERR(pairing_fix_infinity(stat, n, d_P, st), where, err);
+  pi = prof ? prof->begin("verify_wave_pair", st) : -1;
+  hipLaunchKernelGGL(k_wave_miller, g, b, 0, st, 1, (const G1Aff*)d_P, (const LineCoef*)d_lines,
+                     (const WaveJob*)nullptr, (const uint32_t*)nullptr, final_exp, d_out, (int32_t*)nullptr);
+  if (prof) prof->end(pi, st, (double)n);
+  HIP_TRY_ERR(hipGetLastError(), where, err);
+  HIP_TRY_ERR(hipMemcpyAsync(out, d_out, n * 384, hipMemcpyDeviceToHost, st), where, err);
+  HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
+  return ZKFL_OK;
 }
 
 }  // namespace zkfl

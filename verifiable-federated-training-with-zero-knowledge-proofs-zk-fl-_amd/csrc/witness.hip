@@ -23,10 +23,12 @@
 
 #include <cctype>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "common.h"
+#include "devbufs.h"
 #include "field.h"
 #include "fr29.h"
 #include "host_parse.h"
@@ -279,11 +281,6 @@ __global__ __launch_bounds__(256) void k_wit_out(size_t n, uint32_t nw, const Fr
   outs[j][i] = fr29_to_plain(fr29_ld(W[l]));
 }
 
-int hip_err(hipError_t e, const char* where, std::string& err) {
-  err = std::string(where) + ": " + hipGetErrorString(e);
-  return e == hipErrorOutOfMemory ? ZKFL_E_OOM : ZKFL_E_DEVICE;
-}
-
 }  // namespace
 
 struct WProg {
@@ -297,14 +294,10 @@ struct WProg {
   std::vector<Seg> segs;            // level by level
   std::vector<uint32_t> seg_level;  // segs of level L: [seg_level[L], seg_level[L + 1]) -- one launch each
   ProgView view = {};
-  std::vector<void*> allocs;
+  DevBufs dev;  // what view points into
 };
 
-void wprog_free(WProg* p) {
-  if (!p) return;
-  for (void* a : p->allocs) (void)hipFree(a);
-  delete p;
-}
+void wprog_free(WProg* p) { delete p; }
 
 int wprog_inputs_json(const WProg* p, const char* json, std::vector<uint32_t>& out, std::string& err) {
   return inputs_from_json(p->signals, json, out, err);
@@ -327,7 +320,7 @@ int wprog_load(const uint8_t* img, size_t len, hipStream_t st, WProg** out, std:
   WProgHost H;
   int rc = wprog_parse(img, len, H, err);  // csrc/host_parse.cc: every index validated
   if (rc) return rc;
-  WProg* p = new WProg();
+  std::unique_ptr<WProg> p(new WProg());
   p->n_wires = H.n_wires;
   p->n_pub_out = H.n_pub_out;
   p->n_pub_in = H.n_pub_in;
@@ -365,33 +358,25 @@ int wprog_load(const uint8_t* img, size_t len, hipStream_t st, WProg** out, std:
   struct Up {
     const void* src;
     size_t bytes;
-    void** dst;
+    uint8_t** dst;
   };
-  void *d_ops, *d_lcp, *d_tw, *d_tc, *d_as, *d_tm, *d_c;
+  uint8_t *d_ops, *d_lcp, *d_tw, *d_tc, *d_as, *d_tm, *d_c;
   Up ups[] = {{ops, 16ull * p->n_ops, &d_ops},       {lcp, 4ull * (n_lcs + 1), &d_lcp},
               {tw, 4ull * n_terms, &d_tw},            {tc, 32ull * n_terms, &d_tc},
               {as, 4ull * p->n_asserts, &d_as},      {tm, 32ull * n_tmpl, &d_tm},
               {consts.data(), consts.size(), &d_c}};
-  hipError_t e = hipSuccess;
+  const char* const where = "witness program upload";
   for (auto& u : ups) {
-    *u.dst = nullptr;
-    if (e == hipSuccess) e = hipMalloc(u.dst, u.bytes + 16);
-    if (e == hipSuccess) {
-      p->allocs.push_back(*u.dst);
-      if (u.bytes) e = hipMemcpyAsync(*u.dst, u.src, u.bytes, hipMemcpyHostToDevice, st);
-    }
+    HIP_TRY_ERR(p->dev.get(u.dst, u.bytes, 16), where, err);
+    if (u.bytes) HIP_TRY_ERR(hipMemcpyAsync(*u.dst, u.src, u.bytes, hipMemcpyHostToDevice, st), where, err);
   }
   // the coefficients and constants into the witness engine's x 2^261 form
   const size_t n_c = consts.size() / 32;
-  if (e == hipSuccess && n_terms)
+  if (n_terms)
     hipLaunchKernelGGL(k_wit_to_m261, dim3(zk_grid(n_terms, 256)), dim3(256), 0, st, (Fr*)d_tc, (size_t)n_terms);
-  if (e == hipSuccess && n_c) hipLaunchKernelGGL(k_wit_to_m261, dim3(zk_grid(n_c, 256)), dim3(256), 0, st, (Fr*)d_c, n_c);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    wprog_free(p);
-    return hip_err(e, "witness program upload", err);
-  }
+  if (n_c) hipLaunchKernelGGL(k_wit_to_m261, dim3(zk_grid(n_c, 256)), dim3(256), 0, st, (Fr*)d_c, n_c);
+  HIP_TRY_ERR(hipGetLastError(), where, err);
+  HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
   p->view.ops = (const uint4*)d_ops;
   p->view.lc_ptr = (const uint32_t*)d_lcp;
   p->view.term_wire = (const uint32_t*)d_tw;
@@ -400,7 +385,7 @@ int wprog_load(const uint8_t* img, size_t len, hipStream_t st, WProg** out, std:
   p->view.tmpl = (const uint32_t*)d_tm;
   p->view.consts = (const Fr*)d_c;
   p->view.n_wires = p->n_wires;
-  *out = p;
+  *out = p.release();
   return ZKFL_OK;
 }
 
@@ -454,34 +439,32 @@ int wprog_run(const WProg* p, size_t n, const uint8_t* inputs, Fr* const* outs_h
   size_t chunk = (size_t)(2048ull << 20) / (per ? per : 1);
   if (chunk < 1) chunk = 1;
   if (chunk > n) chunk = n;
-  Fr* W = nullptr;
-  uint32_t *d_in = nullptr, *d_fail = nullptr;
-  Fr** d_outs = nullptr;
-  hipError_t e = hipMalloc(&W, chunk * per);
-  if (e == hipSuccess) e = hipMalloc(&d_in, chunk * n_in * 32 + 16);
-  if (e == hipSuccess) e = hipMalloc(&d_fail, chunk * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_outs, chunk * sizeof(Fr*));
+  DevBufs D;
+  Fr* W;
+  uint32_t *d_in, *d_fail;
+  Fr** d_outs;
+  const char* const where = "witness compute";
+  HIP_TRY_ERR(D.get(&W, chunk * nw), where, err);
+  HIP_TRY_ERR(D.get(&d_in, chunk * n_in * 8, 16), where, err);
+  HIP_TRY_ERR(D.get(&d_fail, chunk), where, err);
+  HIP_TRY_ERR(D.get(&d_outs, chunk), where, err);
   std::vector<uint32_t> fails(chunk);
-  int rc = ZKFL_OK;
-  for (size_t off = 0; off < n && e == hipSuccess && rc == ZKFL_OK; off += chunk) {
+  for (size_t off = 0; off < n; off += chunk) {
     const size_t m = (n - off < chunk) ? n - off : chunk;
-    if (n_in) e = hipMemcpyAsync(d_in, inputs + off * n_in * 32, m * n_in * 32, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_outs, outs_host + off, m * sizeof(Fr*), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = wprog_enqueue(p, m, d_in, W, (Fr* const*)d_outs, d_fail, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(fails.data(), d_fail, m * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    for (size_t j = 0; e == hipSuccess && j < m; j++)
+    if (n_in)
+      HIP_TRY_ERR(hipMemcpyAsync(d_in, inputs + off * n_in * 32, m * n_in * 32, hipMemcpyHostToDevice, st), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(d_outs, outs_host + off, m * sizeof(Fr*), hipMemcpyHostToDevice, st), where, err);
+    HIP_TRY_ERR(wprog_enqueue(p, m, d_in, W, (Fr* const*)d_outs, d_fail, st), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(fails.data(), d_fail, m * 4, hipMemcpyDeviceToHost, st), where, err);
+    HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
+    for (size_t j = 0; j < m; j++)
       if (fails[j] != 0xFFFFFFFFu) {
         err = "witness " + std::to_string(off + j) + ": assert constraint #" + std::to_string(fails[j]) +
               " failed (inputs do not satisfy the circuit)";
-        rc = ZKFL_E_CONSTRAINT;
-        break;
+        return ZKFL_E_CONSTRAINT;
       }
   }
-  if (rc == ZKFL_OK && e != hipSuccess) rc = hip_err(e, "witness compute", err);
-  for (void* q : {(void*)W, (void*)d_in, (void*)d_fail, (void*)d_outs})
-    if (q) (void)hipFree(q);
-  return rc;
+  return ZKFL_OK;
 }
 
 hipError_t zk_wtrace_bind_wit(const WtBuf& b) { return zk_wtrace_bind_tu(b); }

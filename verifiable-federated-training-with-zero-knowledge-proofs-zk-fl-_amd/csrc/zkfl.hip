@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "assemble.h"
+#include "devbufs.h"
 #include "glv.h"
 #include "host_parse.h"
 #include "merkle.h"
@@ -51,8 +52,7 @@ int zkfl::fail(int code, const std::string& msg) {
 }
 
 int zkfl::hip_fail(hipError_t e, const char* where) {
-  g_err = std::string(where) + ": " + hipGetErrorString(e);
-  return e == hipErrorOutOfMemory ? ZKFL_E_OOM : ZKFL_E_DEVICE;
+  return hip_rc(e, where, g_err);
 }
 
 namespace {
@@ -67,40 +67,41 @@ template <class F>
 int run_msm_primitive(zkfl_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, uint8_t* out) {
   if (!ctx || !bases || !scalars || !out || n == 0) return fail(ZKFL_E_ARG, "msm: bad args");
   hipStream_t st = ctx->st;
-  MsmBases<F> mb;
-  MsmScratch<F> ms;
-  MsmTail<F> mt;
-  Affine<F>* d_b = nullptr;
-  uint32_t* d_s = nullptr;
-  XYZZ<F>* d_r = nullptr;
-  uint32_t* d_o = nullptr;
-  int rc = ZKFL_OK;
+  struct Engine {  // released on every exit path
+    MsmBases<F> mb;
+    MsmScratch<F> ms;
+    MsmTail<F> mt;
+    ~Engine() {
+      msm_bases_free(mb);
+      msm_scratch_free(ms);
+      msm_tail_free(mt);
+    }
+  } E;
+  DevBufs D;
+  Affine<F>* d_b;
+  uint32_t* d_s;
+  XYZZ<F>* d_r;
+  Affine<F>* d_o;
   const int c = msm_pick_c(n);
-  hipError_t e = msm_bases_alloc(mb, n, c);
-  if (e == hipSuccess) e = msm_scratch_alloc(ms, n, c, st);
-  if (e == hipSuccess) e = msm_tail_alloc(mt, n, c);
-  if (e == hipSuccess) e = hipMalloc(&d_b, n * sizeof(Affine<F>));
-  if (e == hipSuccess) e = hipMalloc(&d_s, n * 32);
-  if (e == hipSuccess) e = hipMalloc(&d_r, sizeof(XYZZ<F>));
-  if (e == hipSuccess) e = hipMalloc(&d_o, sizeof(Affine<F>));
-  if (e == hipSuccess) e = hipMemcpyAsync(d_b, bases, n * sizeof(Affine<F>), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = msm_bases_set(mb, d_b, nullptr, 0xFFFFFFFFu, st);
-  if (e == hipSuccess) e = msm_run(mb, ms, mt, d_s, nullptr, d_r, st, &ctx->prof,
-                                    std::is_same<F, FqOps>::value ? "msm_accumulate_g1" : "msm_accumulate_g2");
-  if (e == hipSuccess) {
-    point_out(st, d_r, 1, d_o);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, sizeof(Affine<F>), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) rc = hip_fail(e, "msm primitive");
-  msm_bases_free(mb);
-  msm_scratch_free(ms);
-  msm_tail_free(mt);
-  for (void* p : {(void*)d_b, (void*)d_s, (void*)d_r, (void*)d_o})
-    if (p) (void)hipFree(p);
-  return rc;
+  const char* const where = "msm primitive";
+  HIP_TRY(msm_bases_alloc(E.mb, n, c), where);
+  HIP_TRY(msm_scratch_alloc(E.ms, n, c, st), where);
+  HIP_TRY(msm_tail_alloc(E.mt, n, c), where);
+  HIP_TRY(D.get(&d_b, n), where);
+  HIP_TRY(D.get(&d_s, n * 8), where);
+  HIP_TRY(D.get(&d_r, 1), where);
+  HIP_TRY(D.get(&d_o, 1), where);
+  HIP_TRY(hipMemcpyAsync(d_b, bases, n * sizeof(Affine<F>), hipMemcpyHostToDevice, st), where);
+  HIP_TRY(hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st), where);
+  HIP_TRY(msm_bases_set(E.mb, d_b, nullptr, 0xFFFFFFFFu, st), where);
+  HIP_TRY(msm_run(E.mb, E.ms, E.mt, d_s, nullptr, d_r, st, &ctx->prof,
+                  std::is_same<F, FqOps>::value ? "msm_accumulate_g1" : "msm_accumulate_g2"),
+          where);
+  point_out(st, d_r, 1, reinterpret_cast<uint32_t*>(d_o));
+  HIP_TRY(hipGetLastError(), where);
+  HIP_TRY(hipMemcpyAsync(out, d_o, sizeof(Affine<F>), hipMemcpyDeviceToHost, st), where);
+  HIP_TRY(hipStreamSynchronize(st), where);
+  return ZKFL_OK;
 }
 
 int pos_ready(zkfl_ctx* ctx) {
@@ -119,29 +120,14 @@ int check_fr_array(const uint8_t* v, size_t count, const char* what) {
   return ZKFL_OK;
 }
 
-// device scratch of one hashing call, freed on every exit path
-struct DevBufs {
-  std::vector<void*> p;
-  ~DevBufs() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  hipError_t get(void** out, size_t bytes) {
-    *out = nullptr;
-    hipError_t e = hipMalloc(out, bytes ? bytes : 32);
-    if (e == hipSuccess) p.push_back(*out);
-    return e;
-  }
-};
-
-
 // leaves (device, Montgomery) -> full padded tree (host, std)
 int tree_from_device_leaves(zkfl_ctx* ctx, DevBufs& B, const Fr* d_leaves, size_t n, uint32_t depth,
                             uint8_t* tree_out) {
   hipStream_t st = ctx->st;
   const size_t nodes = ((size_t)2 << depth) - 1;
   Fr *d_work, *d_tree;
-  HIP_TRY(B.get((void**)&d_work, merkle_work_size(n, depth) * 32), "alloc");
-  HIP_TRY(B.get((void**)&d_tree, nodes * 32), "alloc");
+  HIP_TRY(B.get(&d_work, merkle_work_size(n, depth)), "alloc");
+  HIP_TRY(B.get(&d_tree, nodes), "alloc");
   int pi = ctx->prof.begin("merkle", st);
   HIP_TRY(merkle_build(ctx->pos, d_leaves, n, depth, d_tree, d_work, st), "merkle");
   ctx->prof.end(pi, st, (double)(merkle_work_size(n, depth) - n));
@@ -211,23 +197,19 @@ int zkfl_debug_g1_glv_mul(zkfl_ctx* ctx, size_t n, const uint8_t* points, const 
   }
   HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
   hipStream_t st = ctx->st;
-  uint8_t *d_p = nullptr, *d_k = nullptr, *d_o = nullptr;
-  int rc = ZKFL_OK;
-  hipError_t e = hipMalloc(&d_p, n * 64);
-  if (e == hipSuccess) e = hipMalloc(&d_k, ks.size() * sizeof(GlvScalar));
-  if (e == hipSuccess) e = hipMalloc(&d_o, n * 64);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_p, points, n * 64, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_k, ks.data(), ks.size() * sizeof(GlvScalar), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    debug_glv_mul(st, (uint32_t)n, (const uint32_t*)d_p, (const GlvScalar*)d_k, (uint32_t*)d_o);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, n * 64, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) rc = hip_fail(e, "glv mul");
-  for (void* q : {(void*)d_p, (void*)d_k, (void*)d_o})
-    if (q) (void)hipFree(q);
-  return rc;
+  DevBufs D;
+  uint32_t *d_p, *d_o;
+  GlvScalar* d_k;
+  HIP_TRY(D.get(&d_p, n * 16), "glv mul");
+  HIP_TRY(D.get(&d_k, ks.size()), "glv mul");
+  HIP_TRY(D.get(&d_o, n * 16), "glv mul");
+  HIP_TRY(hipMemcpyAsync(d_p, points, n * 64, hipMemcpyHostToDevice, st), "glv mul");
+  HIP_TRY(hipMemcpyAsync(d_k, ks.data(), ks.size() * sizeof(GlvScalar), hipMemcpyHostToDevice, st), "glv mul");
+  debug_glv_mul(st, (uint32_t)n, d_p, d_k, d_o);
+  HIP_TRY(hipGetLastError(), "glv mul");
+  HIP_TRY(hipMemcpyAsync(out, d_o, n * 64, hipMemcpyDeviceToHost, st), "glv mul");
+  HIP_TRY(hipStreamSynchronize(st), "glv mul");
+  return ZKFL_OK;
 }
 
 const char* zkfl_last_error(void) { return g_err.c_str(); }
@@ -326,8 +308,7 @@ int zkfl_witness_upload(zkfl_ctx* ctx, const zkfl_key* key, const uint8_t* wtns,
   if (e == hipSuccess) e = hipMemcpyAsync(w->d, v.data, (size_t)v.n * 32, hipMemcpyHostToDevice, ctx->st);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
   if (e != hipSuccess) {
-    if (w->d) (void)hipFree(w->d);
-    delete w;
+    zkfl_witness_free(w);
     return hip_fail(e, "witness upload");
   }
   w->pub.assign(v.data + 32, v.data + 32 + (size_t)key->nPub * 32);
@@ -405,28 +386,24 @@ int zkfl_debug_ntt_coset(zkfl_ctx* ctx, uint8_t* data, uint32_t logn, uint32_t n
   const size_t n = (size_t)1 << logn;
   if (vstride < n || vstride > ((size_t)1 << 32)) return fail(ZKFL_E_ARG, "ntt: bad stride");
   hipStream_t st = ctx->st;
-  NttPlan pl;
-  Fr* d = nullptr;
-  const size_t bytes = ((size_t)(nvec - 1) * vstride + n) * 32;
-  int rc = ZKFL_OK;
-  hipError_t e = ntt_plan_alloc(pl, (int)logn, st);
-  if (col_max >= 0) pl.col_max = col_max;
-  if (e == hipSuccess) e = hipMalloc(&d, bytes);
-  if (e == hipSuccess) e = hipMemcpyAsync(d, data, bytes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    for (uint32_t v = 0; v < nvec; v++) fr_std_to_mont(st, d + v * vstride, n);  // the gaps stay as they are
-    e = ntt_coset_shift(pl, d, (int)nvec, vstride, st);
-  }
-  if (e == hipSuccess) {
-    for (uint32_t v = 0; v < nvec; v++) fr_mont_to_std(st, d + v * vstride, n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(data, d, bytes, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) rc = hip_fail(e, "ntt");
-  ntt_plan_free(pl);
-  if (d) (void)hipFree(d);
-  return rc;
+  struct Plan {  // released on every exit path
+    NttPlan pl;
+    ~Plan() { ntt_plan_free(pl); }
+  } P;
+  DevBufs D;
+  Fr* d;
+  const size_t count = (size_t)(nvec - 1) * vstride + n;
+  HIP_TRY(ntt_plan_alloc(P.pl, (int)logn, st), "ntt");
+  if (col_max >= 0) P.pl.col_max = col_max;
+  HIP_TRY(D.get(&d, count), "ntt");
+  HIP_TRY(hipMemcpyAsync(d, data, count * 32, hipMemcpyHostToDevice, st), "ntt");
+  for (uint32_t v = 0; v < nvec; v++) fr_std_to_mont(st, d + v * vstride, n);  // the gaps stay as they are
+  HIP_TRY(ntt_coset_shift(P.pl, d, (int)nvec, vstride, st), "ntt");
+  for (uint32_t v = 0; v < nvec; v++) fr_mont_to_std(st, d + v * vstride, n);
+  HIP_TRY(hipGetLastError(), "ntt");
+  HIP_TRY(hipMemcpyAsync(data, d, count * 32, hipMemcpyDeviceToHost, st), "ntt");
+  HIP_TRY(hipStreamSynchronize(st), "ntt");
+  return ZKFL_OK;
 }
 
 int zkfl_ntt_coset(zkfl_ctx* ctx, uint8_t* data, uint32_t logn) {
@@ -744,21 +721,20 @@ int zkfl_witness_compute(zkfl_ctx* ctx, const zkfl_wprog* prog, size_t n, const 
   uint32_t nw = 0;
   wprog_info(prog->p, &nw, nullptr, nullptr);
   const size_t img = 76 + 32 * (size_t)nw;
-  Fr* d = nullptr;
-  HIP_TRY(hipMalloc(&d, n * (size_t)nw * 32), "witness buffer");
+  DevBufs D;
+  Fr* d;
+  HIP_TRY(D.get(&d, n * (size_t)nw), "witness buffer");
   std::vector<Fr*> outs(n);
   for (size_t j = 0; j < n; j++) outs[j] = d + j * nw;
   std::string err;
-  int rc = wprog_run(prog->p, n, inputs, outs.data(), ctx->st, err);
-  hipError_t e = hipSuccess;
-  for (size_t j = 0; rc == ZKFL_OK && e == hipSuccess && j < n; j++) {
-    wtns_header(wtns_out + j * img, nw);
-    e = hipMemcpyAsync(wtns_out + j * img + 76, outs[j], 32ull * nw, hipMemcpyDeviceToHost, ctx->st);
-  }
-  if (rc == ZKFL_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->st);
-  (void)hipFree(d);
+  const int rc = wprog_run(prog->p, n, inputs, outs.data(), ctx->st, err);
   if (rc != ZKFL_OK) return fail(rc, err);
-  if (e != hipSuccess) return hip_fail(e, "witness download");
+  for (size_t j = 0; j < n; j++) {
+    wtns_header(wtns_out + j * img, nw);
+    HIP_TRY(hipMemcpyAsync(wtns_out + j * img + 76, outs[j], 32ull * nw, hipMemcpyDeviceToHost, ctx->st),
+            "witness download");
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->st), "witness download");
   return ZKFL_OK;
 }
 
@@ -815,11 +791,7 @@ int zkfl_witness_compute_resident(zkfl_ctx* ctx, const zkfl_wprog* prog, const z
     rc = fail(rc, err);
   }
   if (rc != ZKFL_OK) {
-    for (zkfl_witness* w : ws)
-      if (w) {
-        if (w->d) (void)hipFree(w->d);
-        delete w;
-      }
+    for (zkfl_witness* w : ws) zkfl_witness_free(w);
     return rc;
   }
   for (size_t j = 0; j < n; j++) out[j] = ws[j];
@@ -846,8 +818,8 @@ int zkfl_poseidon_batch(zkfl_ctx* ctx, uint32_t arity, size_t n, const uint8_t* 
   if ((rc = pos_ready(ctx))) return rc;
   DevBufs B;
   Fr *d_in, *d_out;
-  HIP_TRY(B.get((void**)&d_in, n * arity * 32), "alloc");
-  HIP_TRY(B.get((void**)&d_out, n * 32), "alloc");
+  HIP_TRY(B.get(&d_in, n * arity), "alloc");
+  HIP_TRY(B.get(&d_out, n), "alloc");
   hipStream_t st = ctx->st;
   HIP_TRY(hipMemcpyAsync(d_in, inputs, n * arity * 32, hipMemcpyHostToDevice, st), "upload");
   int pi = ctx->prof.begin("poseidon", st);
@@ -868,9 +840,9 @@ int zkfl_vector_hash_batch(zkfl_ctx* ctx, uint32_t len, size_t n, const uint8_t*
   DevBufs B;
   Fr *d_in, *d_out, *d_s;
   const size_t nch = (len + VHASH_CHUNK - 1) / VHASH_CHUNK;
-  HIP_TRY(B.get((void**)&d_in, n * len * 32), "alloc");
-  HIP_TRY(B.get((void**)&d_out, n * 32), "alloc");
-  HIP_TRY(B.get((void**)&d_s, n * nch * 32), "alloc");
+  HIP_TRY(B.get(&d_in, n * len), "alloc");
+  HIP_TRY(B.get(&d_out, n), "alloc");
+  HIP_TRY(B.get(&d_s, n * nch), "alloc");
   hipStream_t st = ctx->st;
   HIP_TRY(hipMemcpyAsync(d_in, values, n * len * 32, hipMemcpyHostToDevice, st), "upload");
   int pi = ctx->prof.begin("vector_hash", st);
@@ -889,8 +861,8 @@ int zkfl_merkle_build(zkfl_ctx* ctx, const uint8_t* leaves, size_t n, uint32_t d
   if ((rc = pos_ready(ctx))) return rc;
   DevBufs B;
   Fr *d_raw, *d_leaves;
-  HIP_TRY(B.get((void**)&d_raw, n * 32), "alloc");
-  HIP_TRY(B.get((void**)&d_leaves, n * 32), "alloc");
+  HIP_TRY(B.get(&d_raw, n), "alloc");
+  HIP_TRY(B.get(&d_leaves, n), "alloc");
   if (n) {
     HIP_TRY(hipMemcpyAsync(d_raw, leaves, n * 32, hipMemcpyHostToDevice, ctx->st), "upload");
     HIP_TRY(fr_to_mont_batch(d_raw, n, d_leaves, ctx->st), "leaves");
@@ -909,9 +881,9 @@ int zkfl_dataset_commit(zkfl_ctx* ctx, const uint8_t* values, size_t n, uint32_t
   DevBufs B;
   Fr *d_in, *d_leaves, *d_s;
   const size_t nch = (len + VHASH_CHUNK - 1) / VHASH_CHUNK;
-  HIP_TRY(B.get((void**)&d_in, n * len * 32), "alloc");
-  HIP_TRY(B.get((void**)&d_leaves, n * 32), "alloc");
-  HIP_TRY(B.get((void**)&d_s, n * nch * 32), "alloc");
+  HIP_TRY(B.get(&d_in, n * len), "alloc");
+  HIP_TRY(B.get(&d_leaves, n), "alloc");
+  HIP_TRY(B.get(&d_s, n * nch), "alloc");
   if (n) {
     HIP_TRY(hipMemcpyAsync(d_in, values, n * len * 32, hipMemcpyHostToDevice, ctx->st), "upload");
     int pi = ctx->prof.begin("vector_hash", ctx->st);

@@ -252,8 +252,44 @@ def _buf(n):
     return (C.c_uint8 * n)()
 
 
-class Context:
+def _proofs(out, n) -> list:
+    """n proofs of 256 B out of a call's output buffer."""
+    ob = bytes(out)
+    return [ob[256 * i:256 * i + 256] for i in range(n)]
+
+
+def _proofs_publics(out, pubs, n, k) -> list:
+    """[(proof, [k public ints])] out of a call's proof buffer and its n x k x 32 B of signals."""
+    pb = bytes(pubs)
+    return [(p, _ints(pb[32 * k * i:32 * k * (i + 1)])) for i, p in enumerate(_proofs(out, n))]
+
+
+class _Handle:
+    """An object of the C ABI: its handle `h` and `_free`, the name of the call that releases it."""
+    _free = None
+    h = None
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._free)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Context(_Handle):
     """One device, one HIP stream (one process per GPU for multi-GPU)."""
+    _free = "zkfl_ctx_destroy"
 
     def __init__(self, device: int = 0):
         import weakref
@@ -273,20 +309,7 @@ class Context:
         if self.h:
             for d in list(self._deps):
                 d.close()
-            lib().zkfl_ctx_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+        super().close()
 
     # profiling (bench.py roofline)
     def set_profiling(self, on, serialize: bool = False):
@@ -514,8 +537,7 @@ class Context:
         ws = (_P * max(1, n))(*[w.h for _, w in jobs])
         out = _buf(256 * max(1, n))
         check(lib().zkfl_groth16_prove_multi(self.h, n, keys, ws, rs, out))
-        ob = bytes(out)
-        return [ob[256 * i:256 * i + 256] for i in range(n)]
+        return _proofs(out, n)
 
     def full_prove_multi(self, jobs, rs: bytes | None = None) -> list:
         """jobs: [(ProvingKey, WitnessProgram, input vector bytes)] -> [(proof, [public ints])]
@@ -531,13 +553,7 @@ class Context:
         pubs = (_U8P * max(1, n))(*[C.cast(b, _U8P) for b in pub_bufs])
         out = _buf(256 * max(1, n))
         check(lib().zkfl_groth16_full_prove_multi(self.h, n, keys, progs, ins, rs, out, pubs))
-        ob = bytes(out)
-        res = []
-        for i, (k, _, _) in enumerate(jobs):
-            pb = bytes(pub_bufs[i])
-            res.append((ob[256 * i:256 * i + 256],
-                        [int.from_bytes(pb[32 * j:32 * j + 32], "little") for j in range(k.n_public)]))
-        return res
+        return [(p, _ints(bytes(pub_bufs[i]))[:jobs[i][0].n_public]) for i, p in enumerate(_proofs(out, n))]
 
     def assemble(self, parts: bytes, n_parts: int, rs: bytes) -> list:
         """Split proofs: parts = n x n_parts x 768 B (proof-major, zkfl_groth16_prove_part_batch's
@@ -547,8 +563,7 @@ class Context:
             raise ZkflError(-1, "assemble: parts / rs sizes disagree")
         out = _buf(256 * max(1, n))
         check(lib().zkfl_groth16_assemble(self.h, n, n_parts, parts, rs, out))
-        ob = bytes(out)
-        return [ob[256 * i:256 * i + 256] for i in range(n)]
+        return _proofs(out, n)
 
     def pairing(self, g1: bytes, g2: bytes, final_exp: bool = True) -> bytes:
         """e(P_i, Q_i) for n pairs (std affine); 384 B std Fq12 each (toObject order)."""
@@ -563,9 +578,10 @@ class Context:
 VERIFY_SCHEDULES = {"auto": 0, "lanes": 1, "waves": 2}  # ZKFL_VERIFY_*
 
 
-class VerifyingKey:
+class VerifyingKey(_Handle):
     """A verification key made device-resident (zkfl_vkey_load): vk_bytes is the vk image of
     Context.verify (zkfl.groth16.vk_bytes).  Any number may be resident on a context."""
+    _free = "zkfl_vkey_free"
 
     def __init__(self, ctx: Context, vk_bytes: bytes):
         h = _P()
@@ -577,20 +593,10 @@ class VerifyingKey:
         check(lib().zkfl_vkey_info(h, C.byref(npub)))
         self.n_public = npub.value
 
-    def close(self):
-        if self.h:
-            lib().zkfl_vkey_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ProvingKey:
+class ProvingKey(_Handle):
     """A .zkey made device-resident (bases expanded per MSM window)."""
+    _free = "zkfl_key_free"
 
     def __init__(self, ctx: Context, zkey, shard: int = 0, n_shards: int = 1):
         """zkey: the key bytes, or its path (mapped and parsed on host threads: zkfl_zkey_file_open
@@ -621,17 +627,6 @@ class ProvingKey:
         nv, npub, dom = C.c_uint32(), C.c_uint32(), C.c_uint32()
         check(lib().zkfl_key_info(h, C.byref(nv), C.byref(npub), C.byref(dom)))
         self.n_vars, self.n_public, self.domain_size = nv.value, npub.value, dom.value
-
-    def close(self):
-        if self.h:
-            lib().zkfl_key_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def ab_shared(self) -> dict:
         """How the key holds its A query (zkfl_key_ab_shared): form "D" (A = B1 + sum w_i (A_i - B1_i))
@@ -667,8 +662,7 @@ class ProvingKey:
         arr = (_P * n)(*[w.h for w in ws])
         out = _buf(256 * n)
         check(lib().zkfl_groth16_prove_batch(self.ctx.h, self.h, n, arr, rs, out))
-        ob = bytes(out)
-        return [ob[256 * i:256 * i + 256] for i in range(n)]
+        return _proofs(out, n)
 
     def prove_part_batch(self, ws, rs: bytes) -> list:
         """This shard's parts of n proofs (rs REQUIRED, n x 64 B, the same on every shard)
@@ -690,11 +684,7 @@ class ProvingKey:
         out = _buf(256 * max(1, n))
         pubs = _buf(32 * max(1, self.n_public) * max(1, n))
         check(lib().zkfl_groth16_full_prove_batch(self.ctx.h, self.h, prog.h, n, buf, rs, out, pubs))
-        ob, pb = bytes(out), bytes(pubs)
-        k = self.n_public
-        return [(ob[256 * i:256 * i + 256],
-                 [int.from_bytes(pb[32 * (i * k + j):32 * (i * k + j) + 32], "little") for j in range(k)])
-                for i in range(n)]
+        return _proofs_publics(out, pubs, n, self.n_public)
 
     def full_prove_json_batch(self, prog: "WitnessProgram", texts, rs: bytes | None = None):
         """input.json texts -> [(proof 256 B, [public ints])]: parsed by host threads while earlier
@@ -704,11 +694,7 @@ class ProvingKey:
         out = _buf(256 * max(1, n))
         pubs = _buf(32 * max(1, self.n_public) * max(1, n))
         check(lib().zkfl_groth16_full_prove_json_batch(self.ctx.h, self.h, prog.h, n, arr, rs, out, pubs))
-        ob, pb = bytes(out), bytes(pubs)
-        k = self.n_public
-        return [(ob[256 * i:256 * i + 256],
-                 [int.from_bytes(pb[32 * (i * k + j):32 * (i * k + j) + 32], "little") for j in range(k)])
-                for i in range(n)]
+        return _proofs_publics(out, pubs, n, self.n_public)
 
     def full_prove_json(self, prog: "WitnessProgram", input_json: str, rs: bytes | None = None):
         """snarkjs groth16.fullProve for one input.json text -> (proof 256 B, [public ints])."""
@@ -728,7 +714,9 @@ class ProvingKey:
         return hs, parts
 
 
-class ResidentWitness:
+class ResidentWitness(_Handle):
+    _free = "zkfl_witness_free"
+
     def __init__(self, key: ProvingKey, wtns: bytes | None = None, handle=None):
         if handle is not None:
             self.h = handle
@@ -738,17 +726,6 @@ class ResidentWitness:
         check(lib().zkfl_witness_upload(key.ctx.h, key.h, wtns, len(wtns), C.byref(h)))
         self.h = h
         key.ctx._own(self)
-
-    def close(self):
-        if self.h:
-            lib().zkfl_witness_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def parse_inputs(image: bytes, input_json: str, cap: int | None = None) -> bytes:
@@ -762,9 +739,10 @@ def parse_inputs(image: bytes, input_json: str, cap: int | None = None) -> bytes
     return bytes(out)[:32 * n.value]
 
 
-class WitnessProgram:
+class WitnessProgram(_Handle):
     """A compiled circuit witness program (zkfl.wprog image) loaded on the device: the
     replacement of circom's <circuit>.wasm + generate_witness.cjs."""
+    _free = "zkfl_wprog_free"
 
     def __init__(self, ctx: Context, image: bytes):
         h = _P()
@@ -775,17 +753,6 @@ class WitnessProgram:
         check(lib().zkfl_wprog_info(h, C.byref(nw), C.byref(ni), C.byref(npub)))
         self.n_wires, self.n_inputs, self.n_public = nw.value, ni.value, npub.value
         self.wtns_size = lib().zkfl_wtns_size(h)
-
-    def close(self):
-        if self.h:
-            lib().zkfl_wprog_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _inputs(self, inputs) -> bytes:
         buf = b"".join(inputs)
@@ -844,31 +811,15 @@ def r1cs_header(r1cs: bytes) -> dict:
     return h.as_dict()
 
 
-class R1cs:
+class R1cs(_Handle):
     """A circuit's .r1cs on the device, to check witnesses against (`snarkjs wtns check`)."""
+    _free = "zkfl_r1cs_free"
 
     def __init__(self, ctx: Context, r1cs: bytes):
         h = _P()
         check(lib().zkfl_r1cs_load(ctx.h, r1cs, len(r1cs), C.byref(h)))
         self.h, self.ctx = h, ctx
         ctx._own(self)
-
-    def close(self):
-        if self.h:
-            lib().zkfl_r1cs_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def info(self) -> dict:
         h = R1csHeader()
