@@ -113,6 +113,48 @@ int zkfl_key_ab_shared(const zkfl_key* key, uint32_t* d_form, uint32_t* shared_w
  * augmentation points of bytes 1 | 2, 3 | infinity, infinity | 3 and scalar indices n, n + 1, n + 2. */
 int zkfl_debug_ab_partition(const uint8_t* sec_a, const uint8_t* sec_b1, size_t n, uint32_t shard, uint32_t n_shards,
                             uint32_t* counts, uint32_t* sidx_out, uint8_t* img_out);
+/* Grouped form of the witness queries.  Wires that carry equal values in every
+ * witness of a workload (the twin Poseidon instances of Merkle paths through one tree) need one MSM
+ * base per group: for a partition of the wires with rep(i) the first wire of i's group,
+ *     sum_i w_i P_i = sum_g w_rep(g) S_g + sum_{i non-rep} (w_i - w_rep(i)) P_i,   S_g = sum_{i in g} P_i,
+ * holds for any partition and any witness, and a zero difference costs nothing.  The partition is a
+ * speed hint: proof bytes never depend on it.  Whole proofs on an unsharded key run the grouped
+ * form once the key holds a partition; the parity hook and split proofs keep the plain form.
+ *
+ * zkfl_key_set_groups: rep[n_vars] with rep[i] <= i and rep[rep[i]] == rep[i] (else ZKFL_E_ARG, as
+ * for n_vars != the key's, a sharded key or a key with a proof in flight); a group is further split
+ * so that its first wire has a base in every query in which a member has one.  rep == NULL drops
+ * the grouped form.  Builds the group sums and their window copies on the device (one more
+ * expanded copy of the A, B1, B2 and C + H queries).
+ * zkfl_key_learn_groups: the partition of w's equal values >= 2^128 (host hashing of the
+ * downloaded witness), then as the setter.
+ * A batch call of at least ZKFL_GROUP_MIN_BATCH proofs (default 8) learns from its first witness
+ * when its key is unsharded and holds no partition, and learns again (once per call) when more
+ * than half of the non-representative wires missed in the key's last proof and the partition was
+ * learned; ZKFL_GROUPS=0 (read when the context is made) turns all of it off.  Each build logs
+ * its time to stderr. */
+typedef struct zkfl_groups_info {
+  uint32_t grouped;       /* 1: the key holds a partition */
+  uint32_t learned;       /* 1: learned from a witness, 0: set by the caller */
+  uint32_t groups;        /* groups of more than one wire */
+  uint32_t non_rep;       /* wires that are not their group's first */
+  uint32_t bases[4];      /* A, B1, B2, C + H: bases of the plain form (augmentation and H included) */
+  uint32_t bases_rep[4];  /* of them, those that carry a scalar when the witness follows the partition */
+  uint32_t builds;        /* partitions built on this key so far */
+  uint32_t last_miss;     /* non-zero differences in the key's last finished grouped proof */
+  double build_ms;        /* the last build: host grouping, group sums, expansion */
+} zkfl_groups_info;
+int zkfl_key_set_groups(zkfl_key* key, const uint32_t* rep, size_t n_vars);
+int zkfl_key_learn_groups(zkfl_ctx* ctx, zkfl_key* key, const zkfl_witness* w);
+int zkfl_key_groups(const zkfl_key* key, zkfl_groups_info* out);
+/* The host side of it on caller-supplied data (no device): values (n x 32 B, std form) -> rep_out[n]
+ * (values NULL: rep_out holds the partition on entry), split by sig (n bytes, nullable), then the
+ * grouped form of one query's index map sidx[n_bases] with scalar indices u_base + i:
+ * sidx_out[n_bases], start_out[n_bases + 1], members_out[n_bases] (the first start_out[n_bases] used).
+ * ZKFL_E_ARG for an invalid partition. */
+int zkfl_debug_groups(const uint8_t* values, const uint8_t* sig, size_t n, uint32_t* rep_out, const uint32_t* sidx,
+                      size_t n_bases, uint32_t u_base, uint32_t* sidx_out, uint32_t* start_out,
+                      uint32_t* members_out);
 /* Number of proofs kept in flight by zkfl_groth16_prove_batch (1..32, default 3).  Each slot
  * owns one HIP stream and its own scratch (~0.6 GB for the 2^18 training circuit); proofs in
  * different slots overlap on the GPU.  HIP maps a process's streams onto GPU_MAX_HW_QUEUES

@@ -1,0 +1,286 @@
+// The grouped form of a key's witness queries (csrc/groups.h): its two kernels -- the group sums
+// behind the grouped base sets (once per partition) and the per-proof differences u -- and the
+// key's entry points (set, learn, report).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <chrono>
+#include <cstdio>
+#include <vector>
+
+#include "devbufs.h"
+#include "groups.h"
+#include "objects.h"
+
+using namespace zkfl;
+
+namespace {
+
+// A base coordinate of the window table (the 29-bit engine's Montgomery domain, x 2^261) back to
+// the loader's (x 2^256): fp_mul by 2^251 (< q, one bit)
+ZK_DEV Fq from_m29(const Fq& a) {
+  Fq c = fp_zero<FqP>();
+  c.v[7] = 0x08000000u;
+  return fp_mul(a, c);
+}
+
+template <class F>
+ZK_DEV Affine<F> load_base(const Affine<F>* __restrict__ p) {
+  Affine<F> a = *p;
+  Fq* q = reinterpret_cast<Fq*>(&a);
+#pragma unroll
+  for (int k = 0; k < (int)(sizeof(Affine<F>) / sizeof(Fq)); k++) q[k] = from_m29(q[k]);
+  return a;
+}
+
+// One lane per base slot: its own base, plus its members' with complete additions (equal bases and
+// sums at infinity occur), back to affine with one inversion where there was anything to add.
+template <class F>
+__global__ void __launch_bounds__(64) k_group_sums(const Affine<F>* __restrict__ bases_w, int W, size_t n,
+                                                   const uint32_t* __restrict__ start,
+                                                   const uint32_t* __restrict__ members, Affine<F>* __restrict__ out) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const Affine<F> p = load_base<F>(bases_w + j * W);
+  const uint32_t b = start[j], e = start[j + 1];
+  if (b == e) {
+    out[j] = p;
+    return;
+  }
+  XYZZ<F> acc = xyzz_from_affine<F>(p);
+  for (uint32_t m = b; m < e; m++) acc = xyzz_madd<F>(acc, load_base<F>(bases_w + (size_t)members[m] * W));
+  out[j] = xyzz_to_affine<F>(acc);
+}
+
+constexpr int DELTA_T = 256;
+
+__global__ void __launch_bounds__(DELTA_T) k_group_delta(const Fr* __restrict__ w, const uint32_t* __restrict__ rep,
+                                                         uint32_t n, Fr* __restrict__ u, uint32_t* __restrict__ cnt,
+                                                         uint32_t* __restrict__ miss_out) {
+  ZK_LIGHT();
+  const uint32_t i = blockIdx.x * DELTA_T + threadIdx.x;
+  int nz = 0;
+  if (i < n) {
+    const uint32_t r = rep[i];
+    Fr v = fp_zero<FrP>();
+    if (r != i) {
+      v = fp_sub(w[i], w[r]);
+#pragma unroll
+      for (int k = 0; k < 8; k++) nz |= v.v[k] != 0;
+    }
+    u[i] = v;
+  }
+  const int blk = __syncthreads_count(nz);
+  if (threadIdx.x == 0) {
+    // the last block to arrive publishes the total and leaves both counters zero for the next launch
+    if (blk) atomicAdd(&cnt[0], (uint32_t)blk);
+    __threadfence();
+    if (atomicAdd(&cnt[1], 1u) == gridDim.x - 1) {
+      __threadfence();
+      *miss_out = atomicExch(&cnt[0], 0u);
+      cnt[1] = 0;
+    }
+  }
+}
+
+}  // namespace
+
+namespace zkfl {
+
+template <class F>
+void group_sums(hipStream_t st, const Affine<F>* bases_w, int W, size_t n, const uint32_t* start,
+                const uint32_t* members, Affine<F>* out) {
+  if (n) hipLaunchKernelGGL(k_group_sums<F>, dim3(zk_grid(n, 64)), dim3(64), 0, st, bases_w, W, n, start, members, out);
+}
+template void group_sums<FqOps>(hipStream_t, const G1Aff*, int, size_t, const uint32_t*, const uint32_t*, G1Aff*);
+template void group_sums<Fq2Ops>(hipStream_t, const G2Aff*, int, size_t, const uint32_t*, const uint32_t*, G2Aff*);
+
+void group_delta(hipStream_t st, const Fr* w, const uint32_t* rep, uint32_t n, Fr* u, uint32_t* cnt,
+                 uint32_t* miss_out) {
+  hipLaunchKernelGGL(k_group_delta, dim3(zk_grid(n, DELTA_T)), dim3(DELTA_T), 0, st, w, rep, n, u, cnt, miss_out);
+}
+
+void key_groups_release(zkfl_key* k) {
+  msm_bases_free(k->gA);
+  msm_bases_free(k->gB1);
+  msm_bases_free(k->gB2);
+  msm_bases_free(k->gCH);
+  if (k->grp.d_rep) (void)hipFree(k->grp.d_rep);
+  const uint32_t builds = k->grp.builds;
+  k->grp = KeyGroups();
+  k->grp.builds = builds;
+}
+
+}  // namespace zkfl
+
+namespace {
+
+// One query's grouped base set from its plain one: member lists up, group sums, expansion.
+template <class F>
+hipError_t build_query(const MsmBases<F>& plain, MsmBases<F>& out, const GroupQuery& q, uint32_t extra_start,
+                       DevBufs& D, hipStream_t st) {
+  ZK_CHECK(msm_bases_alloc(out, plain.n, plain.c));
+  if (plain.n == 0) return hipSuccess;
+  uint32_t *d_start, *d_members;
+  Affine<F>* d_img;
+  ZK_CHECK(D.get(&d_start, q.start.size()));
+  ZK_CHECK(D.get(&d_members, q.members.size()));
+  ZK_CHECK(D.get(&d_img, plain.n));
+  ZK_CHECK(hipMemcpyAsync(d_start, q.start.data(), q.start.size() * 4, hipMemcpyHostToDevice, st));
+  if (!q.members.empty())
+    ZK_CHECK(hipMemcpyAsync(d_members, q.members.data(), q.members.size() * 4, hipMemcpyHostToDevice, st));
+  group_sums<F>(st, plain.bases_w, msm_w_of(plain.c), plain.n, d_start, d_members, d_img);
+  ZK_CHECK(hipGetLastError());
+  return msm_bases_set(out, d_img, q.sidx.data(), extra_start, st, false);
+}
+
+// rep: a valid partition of the key's wires (refined here); builds the grouped sets in place of
+// any the key holds.
+int key_build_groups(zkfl_key* k, std::vector<uint32_t>& rep, bool learned, double host_ms) {
+  const auto t0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipSetDevice(k->ctx->device), "hipSetDevice");
+  int rc = key_reset_graphs(k);
+  if (rc) return rc;
+  key_groups_release(k);
+  const uint32_t nV = k->nVars, X = nV, dom = k->n;
+  std::vector<uint8_t> sig(nV, 0);
+  for (int qi = 0; qi < 4; qi++)
+    for (uint32_t i : k->q_sidx[qi])
+      if (i < nV) sig[i] |= (uint8_t)(1u << qi);
+  groups_refine(rep.data(), sig.data(), nV);
+  // u sits behind the four blinding scalars: extra = h + n for A, B1, B2, = h for C + H
+  const uint32_t u_base[4] = {X + 4, X + 4, X + 4, X + dom + 4};
+  GroupQuery q[4];
+  for (int qi = 0; qi < 4; qi++)
+    groups_query(rep.data(), nV, k->q_sidx[qi].data(), k->q_sidx[qi].size(), u_base[qi], q[qi]);
+  hipStream_t st = k->ctx->st;
+  hipError_t e;
+  {
+    DevBufs D;
+    e = hipMalloc(&k->grp.d_rep, (size_t)(nV ? nV : 1) * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(k->grp.d_rep, rep.data(), (size_t)nV * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = build_query(k->bA, k->gA, q[0], X, D, st);
+    if (e == hipSuccess) e = build_query(k->bB1, k->gB1, q[1], X, D, st);
+    if (e == hipSuccess) e = build_query(k->bB2, k->gB2, q[2], X, D, st);
+    if (e == hipSuccess) e = build_query(k->bCH, k->gCH, q[3], X, D, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+  }
+  if (e != hipSuccess) {
+    key_groups_release(k);
+    return hip_fail(e, "grouped base sets");
+  }
+  KeyGroups& g = k->grp;
+  g.on = true;
+  g.learned = learned;
+  for (uint32_t i = 0; i < nV; i++) g.non_rep += rep[i] != i;
+  std::vector<uint8_t> has(nV, 0);
+  for (uint32_t i = 0; i < nV; i++)
+    if (rep[i] != i && !has[rep[i]]) {
+      has[rep[i]] = 1;
+      g.groups++;
+    }
+  for (int qi = 0; qi < 4; qi++) {
+    g.bases[qi] = (uint32_t)k->q_sidx[qi].size();
+    g.bases_rep[qi] = g.bases[qi] - q[qi].non_rep;
+  }
+  g.builds++;
+  g.build_ms = host_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  fprintf(stderr,
+          "zkfl: key of %u wires: %u groups, %u non-representative wires; bases A %u -> %u, B %u -> %u, C+H %u -> %u; "
+          "%s and built in %.1f ms\n",
+          nV, g.groups, g.non_rep, g.bases[0], g.bases_rep[0], g.bases[1], g.bases_rep[1], g.bases[3], g.bases_rep[3],
+          learned ? "learned" : "set", g.build_ms);
+  return ZKFL_OK;
+}
+
+int groups_allowed(const zkfl_key* k) {
+  if (k->nshards != 1) return fail(ZKFL_E_ARG, "groups: a sharded key keeps the plain form");
+  if (!k->ctx->opts.groups) return fail(ZKFL_E_ARG, "groups: turned off on this context (ZKFL_GROUPS=0)");
+  return ZKFL_OK;
+}
+
+}  // namespace
+
+int zkfl::key_learn_groups(zkfl_ctx* ctx, zkfl_key* k, const Fr* d_w) {
+  const auto t0 = std::chrono::steady_clock::now();
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  std::vector<uint32_t> w((size_t)k->nVars * 8), rep;
+  HIP_TRY(hipMemcpy(w.data(), d_w, w.size() * 4, hipMemcpyDeviceToHost), "download witness");
+  groups_learn(w.data(), k->nVars, rep);
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return key_build_groups(k, rep, true, ms);
+}
+
+extern "C" {
+
+int zkfl_key_set_groups(zkfl_key* key, const uint32_t* rep, size_t n_vars) {
+  if (!key) return fail(ZKFL_E_ARG, "null key");
+  if (!rep) {
+    HIP_TRY(hipSetDevice(key->ctx->device), "hipSetDevice");
+    const int rc = key_reset_graphs(key);
+    if (rc) return rc;
+    key_groups_release(key);
+    return ZKFL_OK;
+  }
+  int rc = groups_allowed(key);
+  if (rc) return rc;
+  if (n_vars != key->nVars) return fail(ZKFL_E_ARG, "groups: rep must hold one entry per wire of the key");
+  if (!groups_valid(rep, n_vars)) return fail(ZKFL_E_ARG, "groups: rep[i] <= i and rep[rep[i]] == rep[i] must hold");
+  std::vector<uint32_t> r(rep, rep + n_vars);
+  return key_build_groups(key, r, false, 0.0);
+}
+
+int zkfl_key_learn_groups(zkfl_ctx* ctx, zkfl_key* key, const zkfl_witness* w) {
+  if (!ctx || !key || !w) return fail(ZKFL_E_ARG, "null argument");
+  if (key->ctx != ctx) return fail(ZKFL_E_ARG, "groups: key of another context");
+  if (w->key != key) return fail(ZKFL_E_MISMATCH, "witness uploaded for another key");
+  const int rc = groups_allowed(key);
+  if (rc) return rc;
+  return key_learn_groups(ctx, key, w->d);
+}
+
+int zkfl_key_groups(const zkfl_key* key, zkfl_groups_info* out) {
+  if (!key || !out) return fail(ZKFL_E_ARG, "null argument");
+  const KeyGroups& g = key->grp;
+  *out = zkfl_groups_info();
+  out->grouped = g.on;
+  out->learned = g.learned;
+  out->groups = g.groups;
+  out->non_rep = g.non_rep;
+  for (int i = 0; i < 4; i++) {
+    out->bases[i] = g.on ? g.bases[i] : (uint32_t)key->q_sidx[i].size();
+    out->bases_rep[i] = g.on ? g.bases_rep[i] : out->bases[i];
+  }
+  out->builds = g.builds;
+  out->last_miss = g.last_miss;
+  out->build_ms = g.build_ms;
+  return ZKFL_OK;
+}
+
+int zkfl_debug_groups(const uint8_t* values, const uint8_t* sig, size_t n, uint32_t* rep_out, const uint32_t* sidx,
+                      size_t n_bases, uint32_t u_base, uint32_t* sidx_out, uint32_t* start_out,
+                      uint32_t* members_out) {
+  if (!rep_out || n > 0x7FFFFFF0u || (n_bases && !sidx)) return fail(ZKFL_E_ARG, "debug_groups: bad arguments");
+  std::vector<uint32_t> rep;
+  if (values) {
+    std::vector<uint32_t> w(n * 8);
+    memcpy(w.data(), values, n * 32);
+    groups_learn(w.data(), n, rep);
+  } else {
+    rep.assign(rep_out, rep_out + n);
+    if (!groups_valid(rep.data(), n)) return fail(ZKFL_E_ARG, "debug_groups: not a partition");
+  }
+  if (sig) groups_refine(rep.data(), sig, n);
+  memcpy(rep_out, rep.data(), n * 4);
+  if (sidx_out || start_out || members_out) {
+    GroupQuery q;
+    groups_query(rep.data(), (uint32_t)n, sidx, n_bases, u_base, q);
+    if (sidx_out) memcpy(sidx_out, q.sidx.data(), n_bases * 4);
+    if (start_out) memcpy(start_out, q.start.data(), (n_bases + 1) * 4);
+    if (members_out && !q.members.empty()) memcpy(members_out, q.members.data(), q.members.size() * 4);
+  }
+  return ZKFL_OK;
+}
+
+}  // extern "C"

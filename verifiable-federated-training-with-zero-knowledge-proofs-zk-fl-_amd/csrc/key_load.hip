@@ -32,6 +32,7 @@ void key_release(zkfl_key* k) {
   msm_bases_free(k->bB1);
   msm_bases_free(k->bCH);
   msm_bases_free(k->bB2);
+  key_groups_release(k);
   if (k->dbg_zero) (void)hipFree(k->dbg_zero);
   ntt_plan_free(k->ntt);
   void* ptrs[] = {k->rows, k->cols, k->coefs};
@@ -224,6 +225,9 @@ int zkey_load_parsed(zkfl_ctx* ctx, const ZkeyHost& z, size_t len, double parse_
     }
     mark("bases_upload");
     if (e != hipSuccess) return cleanup(hip_fail(e, "base expansion"));
+    // the index maps stay on the host: a partition's grouped sets are built from them (csrc/groups.hip)
+    if (nshards == 1 && ctx->opts.groups)
+      for (int q = 0; q < NQ; q++) k->q_sidx[q].swap(im[q].sidx);
   }
   KTRY(ntt_plan_alloc(k->ntt, logn, st), "ntt plan");
   if (timing_path) KTRY(hipStreamSynchronize(st), "sync");

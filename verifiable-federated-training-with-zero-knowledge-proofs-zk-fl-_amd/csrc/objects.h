@@ -50,6 +50,8 @@ struct SchedOpts {
   bool fast_wsum = true;  // ZKFL_FAST_WSUM: shorter-chain bucket reduction (latency schedule, small keys)
   int small_logn = 16;    // ZKFL_SMALL_LOGN: a key with a domain <= 2^small_logn is a small key
   bool ab_shared = true;  // ZKFL_AB_SHARED: keys load their A query in D form where that has fewer bases
+  bool groups = true;     // ZKFL_GROUPS: the grouped form of the witness queries (csrc/groups.h)
+  int group_min_batch = 8;  // ZKFL_GROUP_MIN_BATCH: a batch call of at least this many proofs learns a partition
 };
 
 struct zkfl_ctx {
@@ -80,16 +82,20 @@ struct ProofSlot {
   MsmScratch<Fq2Ops> g2s;
   MsmTail<Fq2Ops> g2t;
   Fr* extra = nullptr;  // [4] blinding scalars 1, r, s, -rs (= h + n: the extra slots follow h)
+                        // then, on a key that may hold a partition, u[nVars] (k_group_delta)
   Fr* abc = nullptr;  // [3n]
   Fr* abc_head = nullptr;  // [ceil(K / ABC_L)] ABC segmented-sum partials
   Fr* abc_tail = nullptr;
-  Fr* h = nullptr;    // [n]
+  Fr* h = nullptr;    // [n], then the extra slots
+  uint32_t* grp_cnt = nullptr;  // [2] k_group_delta's counters (left zero by every launch)
+  zkfl_key* key = nullptr;      // the slot's key
+  bool grouped_run = false;     // its in-flight proof runs the grouped form (its miss count is read back)
   G1P* res = nullptr;     // [5]: A', B1', C', H, T
   G2P* resB2 = nullptr;   // [1]
   Fr* d_rs = nullptr;     // r, s (64 B) | GLV halves s1, s2, r1, r2 (4 x 32 B)
   uint32_t* d_parts = nullptr;  // [96]: this rank's part of a split proof (A'|B1'|B2'|C'|H, std affine)
   uint8_t* pinned = nullptr;    // proof (256) | r, s (64) | GLV halves (128) | witness address (8, at
-                                // W_PTR_OFF) | pad | part (768 at 512)
+                                // W_PTR_OFF) | the proof's non-zero u (4, at MISS_OFF) | pad | part (768 at 512)
   // side resources (slot_side_resources): A's and B's own sort scratch, so C + H can sort in g1s
   // while B2 still reads B's pairs -- a small key's slots hold them from the start (run_front),
   // any other slot from its first proof alone (run_lowlat), which also makes that schedule's two
@@ -116,6 +122,20 @@ struct ProofSlot {
   uint8_t* out_part = nullptr;    // split proofs: where the 768 part bytes go (nullable)
 };
 
+// A key's partition of its wires and what was built from it (csrc/groups.hip).
+struct KeyGroups {
+  bool on = false;        // the grouped base sets below the key's plain ones are built
+  bool learned = false;   // from a witness (zkfl_key_learn_groups, a batch call) and not by the caller
+  uint32_t groups = 0;    // groups of more than one wire
+  uint32_t non_rep = 0;   // wires that are not their group's first
+  uint32_t bases[4] = {0, 0, 0, 0};      // A, B1, B2, C + H: bases of the plain form
+  uint32_t bases_rep[4] = {0, 0, 0, 0};  // of them, those that carry a scalar when the witness follows
+  double build_ms = 0;    // the last build: host grouping, group sums, expansion
+  uint32_t builds = 0;
+  uint32_t last_miss = 0;     // non-zero u of the last finished grouped proof
+  uint32_t* d_rep = nullptr;  // [nVars] (device)
+};
+
 struct zkfl_key {
   zkfl_ctx* ctx = nullptr;
   uint32_t nVars = 0, nPub = 0, n = 0;
@@ -132,6 +152,14 @@ struct zkfl_key {
   // Bases: C's (scalars: the private wires) then H's (scalars: h, addressed through the extra
   // pointer = the slot's h vector, whose extra slots 1, r, s, -rs follow it).
   MsmBases<FqOps> bCH;
+  // The grouped form of the four sets (csrc/groups.h): same base count and order, a
+  // representative's slot holds its group's sum, a non-representative's scalar index points at its
+  // u behind the blinding scalars.  Whole proofs on an unsharded key run them (ProofPlan::grouped);
+  // the parity hook and split proofs keep the plain sets.  q_sidx: the plain index maps (host).
+  MsmBases<FqOps> gA, gB1, gCH;
+  MsmBases<Fq2Ops> gB2;
+  KeyGroups grp;
+  std::vector<uint32_t> q_sidx[4];
   // the parity hook's zeros (zkfl_debug_prove_parts, first call, which returns C and H apart): it
   // runs the C + H MSM twice, once with a zero h (C alone) and once with a zero witness (H alone),
   // so the key holds no separate C and H bases (they were ~0.5 GB of expanded bases per key at 2^18)
@@ -187,4 +215,11 @@ void ctx_release(zkfl_ctx* ctx);  // drops one reference; the last one tears the
 // its witness pipe released (key_release, csrc/key_load.hip)
 int get_slot(zkfl_key* k, size_t idx, ProofSlot** out);
 void key_release_slots(zkfl_key* k);
+// its slots' captured graphs dropped (the key's base sets changed); fails on a busy slot
+int key_reset_graphs(zkfl_key* k);
+// csrc/groups.hip: the partition's device state released; a partition learned from the resident
+// witness d_w (nVars std-form values) and built
+void key_groups_release(zkfl_key* k);
+int key_learn_groups(zkfl_ctx* ctx, zkfl_key* k, const Fr* d_w);
+constexpr size_t MISS_OFF = 456;  // ProofSlot::pinned: the proof's count of non-zero u
 }  // namespace zkfl

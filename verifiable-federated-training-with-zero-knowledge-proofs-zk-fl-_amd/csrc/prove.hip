@@ -20,6 +20,7 @@
 
 #include "assemble.h"
 #include "glv.h"
+#include "groups.h"
 #include "host_parse.h"
 #include "objects.h"
 #include "poly.h"
@@ -62,7 +63,7 @@ void slot_release(ProofSlot* s) {
   msm_scratch_free(s->g2s);
   msm_tail_free(s->g2t);
   void* ptrs[] = {s->abc, s->abc_head, s->abc_tail, s->h, s->res, s->resB2, s->d_rs, s->d_parts,
-                  s->w_stage};  // extra lives in h
+                  s->w_stage, s->grp_cnt};  // extra lives in h
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (s->pinned) (void)hipHostFree(s->pinned);
@@ -122,8 +123,13 @@ hipError_t slot_create(zkfl_key* k, ProofSlot** out) {
   }
   if (k->ctx->opts.graph) ZK_CHECK(hipMalloc(&s->w_stage, nV * 32));
   if (k->front) ZK_CHECK(slot_side_resources(s, k, false));  // run_front: C + H sorts in g1s
-  ZK_CHECK(hipMalloc(&s->h, (n + 4) * 32));   // h, then the extra slots (the merged C+H MSM's scalars)
+  // h, then the extra slots (the merged C+H MSM's scalars), then u where the key may hold a partition
+  const bool may_group = k->ctx->opts.groups && k->nshards == 1;
+  ZK_CHECK(hipMalloc(&s->h, (n + 4 + (may_group ? nV : 0)) * 32));
   s->extra = s->h + n;
+  ZK_CHECK(hipMalloc(&s->grp_cnt, 2 * sizeof(uint32_t)));
+  ZK_CHECK(hipMemsetAsync(s->grp_cnt, 0, 2 * sizeof(uint32_t), st));
+  s->key = k;
   ZK_CHECK(hipMalloc(&s->abc, n * 3 * 32));
   const size_t abc_chunks = (k->K + ABC_L - 1) / ABC_L + 1;
   ZK_CHECK(hipMalloc(&s->abc_head, abc_chunks * 32));
@@ -196,6 +202,19 @@ void wpipe_release(WitPipe* p) {
 }
 
 }  // namespace
+
+int zkfl::key_reset_graphs(zkfl_key* k) {
+  for (ProofSlot* s : k->slots)
+    if (s->busy) return fail(ZKFL_E_ARG, "slots busy");
+  for (ProofSlot* s : k->slots) {
+    if (s->st_main) (void)hipStreamSynchronize(s->st_main);
+    if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
+    if (s->graph) (void)hipGraphDestroy(s->graph);
+    s->graph_exec = nullptr;
+    s->graph = nullptr;
+  }
+  return ZKFL_OK;
+}
 
 void zkfl::key_release_slots(zkfl_key* k) {
   wpipe_release(k->wpipe);
@@ -274,13 +293,26 @@ struct ProofPlan {
   bool joint_tails;   // the G2 tail joins the G1 tails' launches (msm_tails_joint)
   bool fast_wsum;     // the shorter-chain bucket reduction (msm.h MSM_WSUM_Q_FAST)
   bool graph;         // replayed from the slot's graph (enqueue_proof_graph), witness staged
+  bool grouped;       // the key's grouped base sets and the differences u (csrc/groups.h)
 };
+
+// The four base sets a plan's proof runs over.
+struct PlanBases {
+  const MsmBases<FqOps>&A, &B1, &CH;
+  const MsmBases<Fq2Ops>& B2;
+};
+inline PlanBases plan_bases(const zkfl_key* k, const ProofPlan& p) {
+  if (p.grouped) return {k->gA, k->gB1, k->gCH, k->gB2};
+  return {k->bA, k->bB1, k->bCH, k->bB2};
+}
 
 // The plan of the next proof of key k on slot s; batch_of_one: it is its batch's only proof.
 ProofPlan plan_proof(const SchedOpts& o, const zkfl_key* k, const ProofSlot* s, ProofMode mode, bool batch_of_one,
                      const Profiler* prof) {
   ProofPlan p = {};
   p.mode = mode;
+  // whole proofs on a key that holds a partition (only unsharded keys do) run the grouped sets
+  p.grouped = mode == ProofMode::Proof && k->grp.on && !ZK_KNOCKOUT;
   // the latency schedule and graph replay serve whole proofs of the plain build on a key whose B
   // queries share a sort; a serialized profile wants one stream, launch by launch
   const bool plain = mode == ProofMode::Proof && k->share_b && !prof->serialize && !ZK_KNOCKOUT;
@@ -376,11 +408,11 @@ hipError_t abc_ntt(zkfl_key* k, ProofSlot* s, const Fr* d_w, hipStream_t st, Pro
 // Step: B2 from B1's sort.  `sorted` holds the pairs of B's digit sort (whoever sorted, on
 // whichever stream, ordered before st here); B2 accumulates from them on st before anything reuses
 // that scratch.  Its tail counts with B1's nnz, copied unless the two alias (ProofSlot::nnz_alias).
-hipError_t b2_from_b1_sort(zkfl_key* k, ProofSlot* s, const MsmScratch<FqOps>& sorted, hipStream_t st,
+hipError_t b2_from_b1_sort(const MsmBases<Fq2Ops>& bB2, ProofSlot* s, const MsmScratch<FqOps>& sorted, hipStream_t st,
                            Profiler* prof) {
   if (!s->nnz_alias)
     ZK_CHECK(hipMemcpyAsync(s->g2t.nnz, s->g1t[1].nnz, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-  return msm_accumulate_sorted(k->bB2, sorted.keys_out, sorted.vals_out, s->g2t, st, prof, "msm_accumulate_g2");
+  return msm_accumulate_sorted(bB2, sorted.keys_out, sorted.vals_out, s->g2t, st, prof, "msm_accumulate_g2");
 }
 
 // Step: what leaves a one-stream schedule -- a split proof's part and its download, a proof's
@@ -422,6 +454,7 @@ int run_lowlat(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Pro
   // the next record, so every wait sees the record it was meant for
   hipEvent_t ev = s->ev_lat[0], ev_b2 = s->ev_lat[1], ev_t = s->ev_lat[2];
   const uint32_t *W = (const uint32_t*)d_w, *E = (const uint32_t*)s->extra;
+  const PlanBases b = plan_bases(k, p);
   MsmTail<FqOps>* tails[3] = {&s->g1t[0], &s->g1t[1], &s->g1t[2]};
   G1P* outs[3] = {s->res + 0, s->res + 1, s->res + 2};
   MsmTail<Fq2Ops>* t2 = &s->g2t;
@@ -429,23 +462,23 @@ int run_lowlat(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Pro
   HIP_TRY(hipEventRecord(ev, st), "event");  // (tails emptied by k_proof_start)
   // lat0: B's sort, then B2 and its tail
   HIP_TRY(hipStreamWaitEvent(sb, ev, 0), "wait");
-  HIP_TRY(msm_sort(k->bB1, s->g1s_b, s->g1t[1].nnz, W, E, sb), "msm B sort");
+  HIP_TRY(msm_sort(b.B1, s->g1s_b, s->g1t[1].nnz, W, E, sb), "msm B sort");
   HIP_TRY(hipEventRecord(ev, sb), "event");
   HIP_TRY(hipStreamWaitEvent(sa, ev, 0), "wait");
-  HIP_TRY(b2_from_b1_sort(k, s, s->g1s_b, sb, prof), "msm B2");
+  HIP_TRY(b2_from_b1_sort(b.B2, s, s->g1s_b, sb, prof), "msm B2");
   HIP_TRY(msm_tails(&t2, &o2, 1, sb, p.fast_wsum), "msm B2 tail");
   HIP_TRY(hipEventRecord(ev_b2, sb), "event");
   // lat1: B1 (B's pairs), A, their tails, then T = s pi_A + r B1 and pi_a
-  HIP_TRY(msm_accumulate_sorted(k->bB1, s->g1s_b.keys_out, s->g1s_b.vals_out, s->g1t[1], sa, prof,
+  HIP_TRY(msm_accumulate_sorted(b.B1, s->g1s_b.keys_out, s->g1s_b.vals_out, s->g1t[1], sa, prof,
                                    "msm_accumulate_g1"), "msm B1");
-  HIP_TRY(msm_accumulate(k->bA, s->g1s_a, s->g1t[0], W, E, sa, prof, "msm_accumulate_g1"), "msm A");
+  HIP_TRY(msm_accumulate(b.A, s->g1s_a, s->g1t[0], W, E, sa, prof, "msm_accumulate_g1"), "msm A");
   HIP_TRY(msm_tails(tails, outs, 2, sa, p.fast_wsum), "msm tails A, B1");
   if (k->a_diff) fold_a(sa, s->res);  // D form: A' = (A' - B1') + B1'
   assemble_t(sa, s->res, glv_halves(s), proof_out(s));
   HIP_TRY(hipEventRecord(ev_t, sa), "event");
   // main: ABC / NTT / h, C + H and its tail, then pi_c and pi_b
   HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
-  HIP_TRY(msm_accumulate(k->bCH, s->g1s, s->g1t[2], W, (const uint32_t*)s->h, st, prof, "msm_accumulate_g1"),
+  HIP_TRY(msm_accumulate(b.CH, s->g1s, s->g1t[2], W, (const uint32_t*)s->h, st, prof, "msm_accumulate_g1"),
           "msm C+H");
   HIP_TRY(msm_tails(&tails[2], &outs[2], 1, st, p.fast_wsum), "msm tail C+H");
   HIP_TRY(hipStreamWaitEvent(st, ev_b2, 0), "wait");
@@ -465,7 +498,8 @@ int run_front(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Prof
   hipStream_t st = s->st_main;
   const uint32_t *W = (const uint32_t*)d_w, *E = (const uint32_t*)s->extra;
   HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
-  const MsmBases<FqOps>* bs[3] = {&k->bA, &k->bB1, &k->bCH};
+  const PlanBases b = plan_bases(k, p);
+  const MsmBases<FqOps>* bs[3] = {&b.A, &b.B1, &b.CH};
   MsmScratch<FqOps>* ss[3] = {&s->g1s_a, &s->g1s_b, &s->g1s};
   MsmTail<FqOps>* tails[3] = {&s->g1t[0], &s->g1t[1], &s->g1t[2]};
   uint32_t* nn[3] = {s->g1t[0].nnz, s->g1t[1].nnz, s->g1t[2].nnz};
@@ -475,7 +509,7 @@ int run_front(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Prof
   const uint16_t* kk[3] = {ss[0]->keys_out, ss[1]->keys_out, ss[2]->keys_out};
   const uint32_t* vv[3] = {ss[0]->vals_out, ss[1]->vals_out, ss[2]->vals_out};
   HIP_TRY(msm_accumulate_sorted_multi(bs, kk, vv, tails, 3, st), "msm A, B1, C+H");
-  HIP_TRY(b2_from_b1_sort(k, s, s->g1s_b, st, prof), "msm B2");
+  HIP_TRY(b2_from_b1_sort(b.B2, s, s->g1s_b, st, prof), "msm B2");
   G1P* outs[3] = {s->res + 0, s->res + 1, s->res + 2};
   MsmTail<Fq2Ops>* t2 = &s->g2t;
   G2P* o2 = s->resB2;
@@ -500,29 +534,30 @@ int run_chain(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Prof
 #else
   MsmScratch<FqOps>&sA = s->g1s, &sB = s->g1s, &sCH = s->g1s;
 #endif
+  const PlanBases b = plan_bases(k, p);
   MsmTail<FqOps>* tails[4] = {&s->g1t[0], &s->g1t[1], &s->g1t[2], &s->g1t[3]};
   G1P* outs[4] = {s->res + 0, s->res + 1, s->res + 2, s->res + 3};
   MsmTail<Fq2Ops>* t2 = &s->g2t;
   G2P* o2 = s->resB2;
   if (!p.share_b_sort && !(ZK_KNOCKOUT & 32))
-    HIP_TRY(msm_run(k->bB2, s->g2s, s->g2t, W, E, s->resB2, st, prof, "msm_accumulate_g2"), "msm B2");
+    HIP_TRY(msm_run(b.B2, s->g2s, s->g2t, W, E, s->resB2, st, prof, "msm_accumulate_g2"), "msm B2");
   if (p.light_first) HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
-  HIP_TRY(msm_accumulate(k->bA, sA, s->g1t[0], W, E, st, prof, "msm_accumulate_g1"), "msm A");
+  HIP_TRY(msm_accumulate(b.A, sA, s->g1t[0], W, E, st, prof, "msm_accumulate_g1"), "msm A");
   if (p.share_b_sort) {  // B2 right after B1, before C + H reuses the sort scratch
-    HIP_TRY(msm_sort(k->bB1, sB, s->g1t[1].nnz, W, E, st), "msm B1 sort");
-    HIP_TRY(msm_accumulate_sorted(k->bB1, sB.keys_out, sB.vals_out, s->g1t[1], st, prof, "msm_accumulate_g1"),
+    HIP_TRY(msm_sort(b.B1, sB, s->g1t[1].nnz, W, E, st), "msm B1 sort");
+    HIP_TRY(msm_accumulate_sorted(b.B1, sB.keys_out, sB.vals_out, s->g1t[1], st, prof, "msm_accumulate_g1"),
             "msm B1");
-    HIP_TRY(b2_from_b1_sort(k, s, sB, st, prof), "msm B2");
+    HIP_TRY(b2_from_b1_sort(b.B2, s, sB, st, prof), "msm B2");
     if (!p.joint_tails) HIP_TRY(msm_tails(&t2, &o2, 1, st, p.fast_wsum), "msm B2 tail");
   } else {
-    HIP_TRY(msm_accumulate(k->bB1, sB, s->g1t[1], W, E, st, prof, "msm_accumulate_g1"), "msm B1");
+    HIP_TRY(msm_accumulate(b.B1, sB, s->g1t[1], W, E, st, prof, "msm_accumulate_g1"), "msm B1");
   }
-  if (parts) HIP_TRY(msm_accumulate(k->bCH, s->g1s, s->g1t[2], W, Z, st, prof, "msm_accumulate_g1"), "msm C");
+  if (parts) HIP_TRY(msm_accumulate(b.CH, s->g1s, s->g1t[2], W, Z, st, prof, "msm_accumulate_g1"), "msm C");
   if (!p.light_first) HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
   if (parts)
-    HIP_TRY(msm_accumulate(k->bCH, s->g1s, s->g1t[3], Z, H, st, prof, "msm_accumulate_g1"), "msm H");
+    HIP_TRY(msm_accumulate(b.CH, s->g1s, s->g1t[3], Z, H, st, prof, "msm_accumulate_g1"), "msm H");
   else
-    HIP_TRY(msm_accumulate(k->bCH, sCH, s->g1t[2], W, H, st, prof, "msm_accumulate_g1"), "msm C+H");
+    HIP_TRY(msm_accumulate(b.CH, sCH, s->g1t[2], W, H, st, prof, "msm_accumulate_g1"), "msm C+H");
   const int ntails = parts ? 4 : 3;
   if (p.joint_tails)
     HIP_TRY(msm_tails_joint(tails, outs, ntails, &t2, &o2, 1, st, p.fast_wsum), "msm tails (G1 + G2)");
@@ -536,6 +571,11 @@ int run_proof(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, const Pro
   Profiler* prof = &ctx->prof;
   const int pp = prof->begin("prove", s->st_main);
   start(k, s, p);
+  // the differences u behind the blinding scalars, from the witness the schedule reads (a
+  // graph-replayed proof's stage, just filled by k_proof_start), before any MSM of any stream
+  if (p.grouped)
+    group_delta(s->st_main, d_w, k->grp.d_rep, k->nVars, s->extra + 4, s->grp_cnt,
+                reinterpret_cast<uint32_t*>(s->pinned + MISS_OFF));
   const int rc = p.schedule == Schedule::Lowlat  ? run_lowlat(k, s, d_w, p, prof)
                  : p.schedule == Schedule::Front ? run_front(k, s, d_w, p, prof)
                                                  : run_chain(k, s, d_w, p, prof);
@@ -578,6 +618,7 @@ int enqueue_proof(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, const
   glv_split(rs_host + 8, ks[0], ks[1]);  // s -> s1, s2 (for pi_A, phi(pi_A))
   glv_split(rs_host, ks[2], ks[3]);      // r -> r1, r2 (for B1, phi(B1))
   const ProofPlan p = plan_proof(ctx->opts, k, s, mode, batch_of_one, &ctx->prof);
+  s->grouped_run = p.grouped;
   int rc;
   if (p.graph) {
     // the witness is staged into the slot's own buffer so the captured kernel arguments hold for
@@ -617,6 +658,8 @@ int wait_slot(ProofSlot* s, bool poll = false) {
   HIP_TRY(host_wait(s->ev_done, poll), "sync");
   if (s->out_proof) memcpy(s->out_proof, s->pinned, 256);
   if (s->out_part) memcpy(s->out_part, s->pinned + 512, PART_WORDS * 4);
+  if (s->grouped_run) memcpy(&s->key->grp.last_miss, s->pinned + MISS_OFF, 4);
+  s->grouped_run = false;
   s->busy = false;
   return ZKFL_OK;
 }
@@ -631,6 +674,20 @@ struct Job {
   uint8_t* proof_out = nullptr;
   uint8_t* part_out = nullptr;  // split proof: this shard's part instead of a proof
 };
+
+// A batch call of at least SchedOpts::group_min_batch proofs meets key J.key for the first time: an
+// unsharded key without a partition learns one from this job's witness, and a key whose learned
+// partition missed on more than half of its non-representative wires in its last proof learns
+// again (once per call: a key is met once).  A single proof never pays for learning.
+int learn_for_batch(zkfl_ctx* ctx, const Job& J, size_t n) {
+  zkfl_key* k = J.key;
+  if (!ctx->opts.groups || ZK_KNOCKOUT || n < (size_t)ctx->opts.group_min_batch || k->nshards != 1 || J.part_out)
+    return ZKFL_OK;
+  const KeyGroups& g = k->grp;
+  if (g.on && !(g.learned && 2 * (uint64_t)g.last_miss > g.non_rep)) return ZKFL_OK;
+  if (J.w_ready) HIP_TRY(hipEventSynchronize(J.w_ready), "wait for the witness group");
+  return key_learn_groups(ctx, k, J.w);
+}
 
 // The batch scheduler behind every prove entry point: job i goes to the next slot of its key
 // (round robin per key), a busy slot is drained first, so up to max_slots proofs per key are in
@@ -683,6 +740,8 @@ int run_jobs(zkfl_ctx* ctx, size_t n, GetJob job) {
     if (c == cursor.size()) {
       cursor.emplace_back();
       cursor.back().key = J.key;
+      rc = learn_for_batch(ctx, J, n);  // before the call enqueues anything on this key
+      if (rc) break;
     }
     rc = issue(cursor[c], i, J, rsl);
   }

@@ -245,6 +245,8 @@ int zkfl_ctx_create(int device, zkfl_ctx** out) {
   ctx->opts.fast_wsum = env("ZKFL_FAST_WSUM", 1) != 0;
   ctx->opts.small_logn = env("ZKFL_SMALL_LOGN", 16);
   ctx->opts.ab_shared = env("ZKFL_AB_SHARED", 1) != 0;
+  ctx->opts.groups = env("ZKFL_GROUPS", 1) != 0;
+  ctx->opts.group_min_batch = std::max(1, env("ZKFL_GROUP_MIN_BATCH", 8));
   hipError_t e = hipStreamCreateWithFlags(&ctx->st, hipStreamNonBlocking);
   if (e != hipSuccess) {
     delete ctx;

@@ -65,6 +65,16 @@ class ZkeyReport(C.Structure):
                 ("coef_matrix", C.c_uint32), ("coef_row", C.c_uint32), ("coef_count", C.c_uint32)]
 
 
+GROUP_QUERIES = ("A", "B1", "B2", "CH")
+
+
+class GroupsInfo(C.Structure):
+    """zkfl_groups_info"""
+    _fields_ = [("grouped", C.c_uint32), ("learned", C.c_uint32), ("groups", C.c_uint32), ("non_rep", C.c_uint32),
+                ("bases", C.c_uint32 * 4), ("bases_rep", C.c_uint32 * 4), ("builds", C.c_uint32),
+                ("last_miss", C.c_uint32), ("build_ms", C.c_double)]
+
+
 # every exported symbol of include/zkfl.h with (restype, argtypes)
 SIGNATURES = {
     "zkfl_version": (C.c_int, []),
@@ -91,6 +101,12 @@ SIGNATURES = {
     "zkfl_key_ab_shared": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "zkfl_debug_ab_partition": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _U8P]),
+    "zkfl_key_set_groups": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_size_t]),
+    "zkfl_key_learn_groups": (C.c_int, [_P, _P, _P]),
+    "zkfl_key_groups": (C.c_int, [_P, C.POINTER(GroupsInfo)]),
+    "zkfl_debug_groups": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                    C.c_size_t, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_uint32)]),
     "zkfl_key_set_slots": (C.c_int, [_P, C.c_int]),
     "zkfl_groth16_prove": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, C.c_char_p, _U8P, _U8P,
                                      C.POINTER(C.c_size_t)]),
@@ -634,6 +650,29 @@ class ProvingKey(_Handle):
         d, sh, nb = C.c_uint32(), C.c_uint32(), C.c_uint32()
         check(lib().zkfl_key_ab_shared(self.h, C.byref(d), C.byref(sh), C.byref(nb)))
         return {"form": "D" if d.value else "A", "shared_wires": sh.value, "a_bases": nb.value}
+
+    def set_groups(self, rep):
+        """The key's partition of its wires (zkfl_key_set_groups): rep[i] = the first wire of i's
+        group, one entry per wire; None drops the grouped form.  Proof bytes do not depend on it."""
+        if rep is None:
+            check(lib().zkfl_key_set_groups(self.h, None, 0))
+            return
+        arr = (C.c_uint32 * max(1, len(rep)))(*rep)
+        check(lib().zkfl_key_set_groups(self.h, arr, len(rep)))
+
+    def learn_groups(self, w: "ResidentWitness"):
+        """Partition the wires by w's equal values >= 2^128 (zkfl_key_learn_groups)."""
+        check(lib().zkfl_key_learn_groups(self.ctx.h, self.h, w.h))
+
+    def groups(self) -> dict:
+        """The key's partition (zkfl_key_groups): groups, non-representative wires, per query the
+        bases of the plain form and those that still carry a scalar, the build time, and the
+        non-zero differences of the key's last grouped proof."""
+        g = GroupsInfo()
+        check(lib().zkfl_key_groups(self.h, C.byref(g)))
+        return {"grouped": bool(g.grouped), "learned": bool(g.learned), "groups": g.groups, "non_rep": g.non_rep,
+                "bases": dict(zip(GROUP_QUERIES, g.bases)), "bases_rep": dict(zip(GROUP_QUERIES, g.bases_rep)),
+                "builds": g.builds, "last_miss": g.last_miss, "build_ms": g.build_ms}
 
     def set_slots(self, slots: int):
         """Proofs kept in flight by prove_batch (each slot = 3 HIP streams + scratch)."""
