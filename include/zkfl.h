@@ -74,6 +74,8 @@ int zkfl_ctx_set_profiling(zkfl_ctx* ctx, int enabled);
 /* name: "msm_accumulate_g1", "msm_accumulate_g2", "ntt", "abc", "prove", "witness" (full-prove
  * slots), "r1cs_terms", "r1cs_verdict" (the witness check's two passes), "verify_wave_g2",
  * "verify_wave_inputs", "verify_wave_pair" (the wave verifier's three kernels; units: proofs),
+ * "verify_round_screen", "verify_round_pair", "verify_round_reduce", "verify_round_final" (the
+ * combined round check's stages; units: proofs),
  * "keycheck_points", "keycheck_rows", "keycheck_msm", "keycheck_pairing" (the key check's stages).
  * Synchronises the device.
  * total_ms: summed event time; units: summed algorithmic units (MSM entries, NTT elements...);
@@ -484,6 +486,48 @@ int zkfl_vkey_free(zkfl_vkey* key);
 #define ZKFL_VERIFY_AUTO_WAVES_MAX 4096
 int zkfl_groth16_verify_multi(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
                               const size_t* npubs, const uint8_t* proofs, int32_t* results, int schedule);
+/* The same jobs, verdicts and argument checks as zkfl_groth16_verify_multi (a key above
+ * ZKFL_VERIFY_WAVE_MAX_PUBLIC is served like any other), answered for the whole round by one
+ * random combination (csrc/verify_round.hip) -- the batched Groth16 verifier:
+ *
+ *   prod_i e(z_i (-A_i), B_i) * prod_k [ e(Z_k alpha_k, beta_k) e(X_k, gamma_k) e(C_k, delta_k) ] == 1
+ *   Z_k = sum z_i mod r,  X_k = sum z_i vk_x_i,  C_k = sum z_i C_i   (sums over key k's jobs)
+ *
+ * one Miller pair per proof, three per key and one final exponentiation per round, where
+ * verify_multi pays three pairs and a final exponentiation per proof.
+ *
+ * Screening: a job with a public signal >= r, a proof coordinate >= q, pi_a or pi_c off the curve,
+ * pi_b off the twist or outside the order-r subgroup gets result 0 and stays out of the
+ * combination (the subgroup test is what the bound below rests on).  A pair whose pi_a or pi_b is
+ * infinity contributes 1, as in zkfl_groth16_verify_batch.
+ * Verdict: when the combination is 1 every combined job gets result 1.  Otherwise the combined jobs
+ * are verified one by one as zkfl_groth16_verify_multi does under ZKFL_VERIFY_AUTO and get its
+ * verdicts.  If every combined proof is valid the combination is 1; if one is not it is 1 with
+ * probability <= 2^-128 over the z_i, so the results equal verify_multi's up to that probability.
+ * Cost of a bad proof: a single invalid proof that passes the screening costs the round the
+ * combined pass plus the per-proof pass.  Narrowing the bad jobs down by bisection is not done.
+ *
+ * z NULL: each z_i is drawn uniformly from [0, 2^128) with the OS CSPRNG inside the call (as
+ * rs == NULL for proofs).  A caller's z (n x 16 B little endian) is for tests and forfeits
+ * soundness: proofs can be made to cancel under values known in advance.
+ * report (nullable): filled on ZKFL_OK. */
+typedef struct {
+  uint32_t keys;     /* distinct keys among the jobs */
+  uint32_t screened; /* jobs rejected by the encoding checks (result 0, not combined) */
+  uint32_t combined; /* jobs that entered the combination */
+  uint32_t passed;   /* 1: the combination equals 1 */
+  uint32_t fallback; /* jobs re-verified one by one (0 when passed) */
+} zkfl_round_report;
+int zkfl_groth16_verify_round(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
+                              const size_t* npubs, const uint8_t* proofs, const uint8_t* z, int32_t* results,
+                              zkfl_round_report* report);
+/* Parity hook: the final-exponentiated combination of the jobs that pass the screening, 384 B in
+ * zkfl_pairing's layout, and screened_out[i] = 1 for the jobs that do not.  z is required.  chunk:
+ * how many proofs one pass holds the lines of pi_b for (0 = the production value, 4096: 80 MB of
+ * lines); a small value makes a small round take several passes. */
+int zkfl_debug_verify_round(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
+                            const size_t* npubs, const uint8_t* proofs, const uint8_t* z, size_t chunk,
+                            uint8_t gt_out[384], int32_t* screened_out);
 /* Parity hook: zkfl_pairing (final_exp != 0) / zkfl_debug_miller_loop (final_exp == 0) computed by
  * the wave path's tower, Miller loop and final exponentiation; same inputs, layout and errors. */
 int zkfl_debug_wave_pairing(zkfl_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2, int final_exp,

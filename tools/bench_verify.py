@@ -8,6 +8,10 @@ correctness gate in SURVEY.md §8 a9, not the metric).
     bench_verify.py [sizes..]            one key, zkfl_groth16_verify_batch
     bench_verify.py --multi [sizes..]    two resident keys, zkfl_groth16_verify_multi: one line per
                                          (schedule, n), lanes and waves in the same process
+    bench_verify.py --round [sizes..]    the --multi setup; per n one line each for lanes, waves and the
+                                         combined call (zkfl_groth16_verify_round) in the same process,
+                                         the combined call's per-stage records, and one round with a
+                                         single invalid proof (the fallback's cost)
 """
 import json
 import os
@@ -15,19 +19,15 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "verifiable-federated-training-with-zero-knowledge-proofs-zk-fl-_amd"))
+sys.path[:0] = [os.path.join(ROOT, "verifiable-federated-training-with-zero-knowledge-proofs-zk-fl-_amd"), ROOT]
 
 from zkfl import circuits, clients, groth16, native, wprog  # noqa: E402
 from zkfl import zkey  # noqa: E402
 
 
-def multi(sizes, repeats=10):
-    """--multi: a round's proofs against two resident keys, sgd_verified(8,4,3) and
-    secure_masked_update(4,7) (bench.py config 5's pair), interleaved as a round interleaves them
-    (training, secure aggregation, training, ...).  One JSON line per (schedule, n): median, min and
-    max wall time of `repeats` verify_multi calls after one warm-up call, same process, same jobs."""
-    import statistics
-    ctx = native.Context(0)
+def _two_keys(ctx):
+    """Two resident keys with one valid proof each: sgd_verified(8,4,3) and secure_masked_update(4,7)
+    (bench.py config 5's pair) -> [(VerifyingKey, public bytes, proof bytes)]."""
     tr, sa, _ = clients.federated_round(8, rnd=1)[0]
     made = []
     for i, (b, inp) in enumerate(((circuits.build("sgd_verified", 8, 4, 3, 1000), tr),
@@ -40,19 +40,35 @@ def multi(sizes, repeats=10):
         key.close()
         vk = native.VerifyingKey(ctx, groth16.vk_bytes(groth16.export_verification_key(zk, alphabeta=False)))
         made.append((vk, groth16.public_bytes(pub), proof))
+    return made
+
+
+def _timed(label, n, made, call, want, repeats, **extra):
+    """One JSON line: median, min and max wall time of `repeats` calls after one warm-up call whose
+    verdicts are checked."""
+    import statistics
+    assert call() == want, label  # warm-up, and the verdicts
+    ts = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        call()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    print(json.dumps({"schedule": label, "n": n, "median_ms": round(statistics.median(ts), 3),
+                      "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3), "repeats": repeats,
+                      "npub": [made[0][0].n_public, made[1][0].n_public], **extra,
+                      "build": native.build_id()}), flush=True)
+
+
+def multi(sizes, repeats=10):
+    """--multi: a round's proofs against the two keys, interleaved as a round interleaves them
+    (training, secure aggregation, training, ...).  One JSON line per (schedule, n): median, min and
+    max wall time of `repeats` verify_multi calls after one warm-up call, same process, same jobs."""
+    ctx = native.Context(0)
+    made = _two_keys(ctx)
     for n in sizes:
         jobs = [made[i % 2] for i in range(n)]
         for sched in ("lanes", "waves"):
-            assert all(ctx.verify_multi(jobs, sched))  # warm-up, and the verdicts
-            ts = []
-            for _ in range(repeats):
-                t0 = time.perf_counter()
-                ctx.verify_multi(jobs, sched)
-                ts.append((time.perf_counter() - t0) * 1e3)
-            print(json.dumps({"schedule": sched, "n": n, "median_ms": round(statistics.median(ts), 3),
-                              "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3), "repeats": repeats,
-                              "npub": [made[0][0].n_public, made[1][0].n_public],
-                              "build": native.build_id()}), flush=True)
+            _timed(sched, n, made, lambda: ctx.verify_multi(jobs, sched), [True] * n, repeats)
     # where the wave path's time goes: per-kernel event times of one proof and of a round of 16
     for n in (1, 16):
         ctx.set_profiling(True)
@@ -64,7 +80,41 @@ def multi(sizes, repeats=10):
     ctx.close()
 
 
+ROUND_RECORDS = ("verify_round_screen", "verify_round_pair", "verify_round_reduce", "verify_round_final")
+
+
+def round_(sizes, repeats=10):
+    """--round: --multi's jobs under lanes, waves and the combined call, same process; then the
+    combined call's per-stage event times, and the round with its last proof made invalid (pi_c + G:
+    it passes the screening, so the combination fails and every job is verified again one by one)."""
+    ctx = native.Context(0)
+    made = _two_keys(ctx)
+    vk, pub, proof = made[1]
+    c = int.from_bytes(proof[192:224], "little"), int.from_bytes(proof[224:256], "little")
+    from oracle import bn254 as bn
+    bad_c = bn.add(c, bn.G1_GEN)
+    bad = (vk, pub, proof[:192] + bad_c[0].to_bytes(32, "little") + bad_c[1].to_bytes(32, "little"))
+    for n in sizes:
+        jobs = [made[i % 2] for i in range(n)]
+        for sched in ("lanes", "waves"):
+            _timed(sched, n, made, lambda: ctx.verify_multi(jobs, sched), [True] * n, repeats)
+        _timed("combined", n, made, lambda: ctx.verify_round(jobs)[0], [True] * n, repeats)
+        ctx.set_profiling(True)
+        ctx.profile_reset()
+        _, rep = ctx.verify_round(jobs)
+        prof = {k: round(ctx.profile(k)[0], 3) for k in ROUND_RECORDS}
+        ctx.set_profiling(False)
+        print(json.dumps({"profile_ms": prof, "n": n, "report": rep}), flush=True)
+        one_bad = jobs[:-1] + [bad]
+        _, rep = ctx.verify_round(one_bad)
+        _timed("combined, one invalid proof", n, made, lambda: ctx.verify_round(one_bad)[0],
+               [True] * (n - 1) + [False], repeats, report=rep)
+    ctx.close()
+
+
 def main():
+    if "--round" in sys.argv[1:]:
+        return round_([int(x) for x in sys.argv[1:] if x != "--round"] or [16, 256, 1024, 4096])
     if "--multi" in sys.argv[1:]:
         return multi([int(x) for x in sys.argv[1:] if x != "--multi"] or [1, 16, 64, 256, 1024, 4096])
     sizes = [int(x) for x in (sys.argv[1:] or ["1", "64", "1024", "8192"])]

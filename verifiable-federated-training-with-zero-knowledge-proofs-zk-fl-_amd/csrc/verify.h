@@ -48,4 +48,16 @@ int verify_wave(size_t n, const VerifyJob* jobs, const uint8_t* proofs, int32_t*
 int pairing_wave_batch(size_t n, const uint8_t* g1, const uint8_t* g2, int final_exp, uint8_t* out, hipStream_t st,
                        Profiler* prof, std::string& err);
 
+// ---- a round as one random combination (csrc/verify_round.hip) ----
+// Screens every job by verify_batch's encoding rules (screened[i] = 1: rejected, not combined) and
+// forms prod_i e(z_i (-A_i), B_i) prod_k e(S_k, beta_k) e(X_k, gamma_k) e(C_k, delta_k) over the
+// others; one final exponentiation.  z: n x 16 B little endian (never null here).  chunk: proofs
+// per pass (0 = 4096; at most ROUND_MAX_CHUNK).  gt_out (nullable): the value, 384 B in
+// pairing_batch's layout; *passed = (value == 1); *nkeys = distinct keys.  jobs[i].wtab is not read.
+// prof (nullable): "verify_round_*" records.
+constexpr size_t ROUND_MAX_CHUNK = 65536;
+int verify_round(size_t n, const VerifyJob* jobs, const uint8_t* proofs, const uint8_t* z, size_t chunk,
+                 uint8_t* gt_out, int32_t* screened, int* passed, uint32_t* nkeys, hipStream_t st, Profiler* prof,
+                 std::string& err);
+
 }  // namespace zkfl

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <sys/random.h>
 
 #include <algorithm>
 #include <cstdlib>
@@ -587,23 +588,24 @@ int zkfl_vkey_free(zkfl_vkey* key) {
   return ZKFL_OK;
 }
 
-int zkfl_groth16_verify_multi(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
-                              const size_t* npubs, const uint8_t* proofs, int32_t* results, int schedule) {
-  if (!ctx || (n && (!vkeys || !pubs || !npubs || !proofs || !results)))
-    return fail(ZKFL_E_ARG, "verify_multi: null argument");
-  if (schedule != ZKFL_VERIFY_AUTO && schedule != ZKFL_VERIFY_LANES && schedule != ZKFL_VERIFY_WAVES)
-    return fail(ZKFL_E_ARG, "verify_multi: unknown schedule " + std::to_string(schedule));
+// The per-job argument checks of the multi-key entry points (fn names the caller in the message)
+static int verify_jobs_check(const char* fn, zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys,
+                             const uint8_t* const* pubs, const size_t* npubs) {
+  const std::string who = std::string(fn) + ": job ";
   for (size_t i = 0; i < n; i++) {
-    if (!vkeys[i] || vkeys[i]->ctx != ctx)
-      return fail(ZKFL_E_ARG, "verify_multi: job " + std::to_string(i) + " has no key of this context");
+    if (!vkeys[i] || vkeys[i]->ctx != ctx) return fail(ZKFL_E_ARG, who + std::to_string(i) + " has no key of this context");
     const uint32_t want = vk_npub(vkeys[i]->vk);
     if (npubs[i] != want)
-      return fail(ZKFL_E_MISMATCH, "verify_multi: job " + std::to_string(i) + " has " + std::to_string(npubs[i]) +
+      return fail(ZKFL_E_MISMATCH, who + std::to_string(i) + " has " + std::to_string(npubs[i]) +
                                        " public signals, its key expects " + std::to_string(want));
-    if (want && !pubs[i]) return fail(ZKFL_E_ARG, "verify_multi: job " + std::to_string(i) + " has null publics");
+    if (want && !pubs[i]) return fail(ZKFL_E_ARG, who + std::to_string(i) + " has null publics");
   }
-  if (n == 0) return ZKFL_OK;
-  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  return ZKFL_OK;
+}
+
+// n > 0 checked jobs by one of the schedules; the device is set
+static int verify_multi_run(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
+                            const uint8_t* proofs, int32_t* results, int schedule) {
   if (schedule == ZKFL_VERIFY_AUTO)
     schedule = n <= ZKFL_VERIFY_AUTO_WAVES_MAX ? ZKFL_VERIFY_WAVES : ZKFL_VERIFY_LANES;
   // the wave jobs, in job order; every other job by key, in order of first appearance
@@ -655,6 +657,102 @@ int zkfl_groth16_verify_multi(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* v
     for (size_t j = 0; j < idx.size(); j++) res[idx[j]] = part[j];
   }
   memcpy(results, res.data(), n * sizeof(int32_t));
+  return ZKFL_OK;
+}
+
+int zkfl_groth16_verify_multi(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
+                              const size_t* npubs, const uint8_t* proofs, int32_t* results, int schedule) {
+  if (!ctx || (n && (!vkeys || !pubs || !npubs || !proofs || !results)))
+    return fail(ZKFL_E_ARG, "verify_multi: null argument");
+  if (schedule != ZKFL_VERIFY_AUTO && schedule != ZKFL_VERIFY_LANES && schedule != ZKFL_VERIFY_WAVES)
+    return fail(ZKFL_E_ARG, "verify_multi: unknown schedule " + std::to_string(schedule));
+  if (const int rc = verify_jobs_check("verify_multi", ctx, n, vkeys, pubs, npubs)) return rc;
+  if (n == 0) return ZKFL_OK;
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  return verify_multi_run(ctx, n, vkeys, pubs, proofs, results, schedule);
+}
+
+// A round as one random combination (csrc/verify_round.hip).  screened: n flags; *passed: the
+// combination is 1.
+static int verify_round_combine(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
+                                const uint8_t* proofs, const uint8_t* z, size_t chunk, uint8_t* gt_out,
+                                int32_t* screened, int* passed, uint32_t* nkeys) {
+  std::vector<uint8_t> drawn;
+  if (!z) {  // CSPRNG, as rs == NULL for proofs; every 128-bit value is a valid z
+    drawn.resize(16 * n);
+    for (size_t got = 0; got < drawn.size();) {
+      const size_t want = std::min<size_t>(256, drawn.size() - got);
+      if (getrandom(drawn.data() + got, want, 0) != (ssize_t)want) return fail(ZKFL_E_DEVICE, "getrandom failed");
+      got += want;
+    }
+    z = drawn.data();
+  }
+  std::vector<VerifyJob> jobs(n);
+  for (size_t i = 0; i < n; i++) jobs[i] = {vkeys[i]->vk, vkeys[i]->wtab, pubs[i]};
+  std::string err;
+  const int rc = verify_round(n, jobs.data(), proofs, z, chunk, gt_out, screened, passed, nkeys, ctx->st, &ctx->prof,
+                              err);
+  return rc == ZKFL_OK ? rc : fail(rc, err);
+}
+
+int zkfl_groth16_verify_round(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
+                              const size_t* npubs, const uint8_t* proofs, const uint8_t* z, int32_t* results,
+                              zkfl_round_report* report) {
+  if (!ctx || (n && (!vkeys || !pubs || !npubs || !proofs || !results)))
+    return fail(ZKFL_E_ARG, "verify_round: null argument");
+  if (const int rc = verify_jobs_check("verify_round", ctx, n, vkeys, pubs, npubs)) return rc;
+  zkfl_round_report rep = {0, 0, 0, 1, 0};
+  if (n == 0) {
+    if (report) *report = rep;
+    return ZKFL_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  std::vector<int32_t> screened(n, 0), res(n, 0);
+  int passed = 0;
+  int rc = verify_round_combine(ctx, n, vkeys, pubs, proofs, z, 0, nullptr, screened.data(), &passed, &rep.keys);
+  if (rc != ZKFL_OK) return rc;
+  std::vector<size_t> comb;
+  for (size_t i = 0; i < n; i++)
+    if (!screened[i]) comb.push_back(i);
+  rep.screened = (uint32_t)(n - comb.size());
+  rep.combined = (uint32_t)comb.size();
+  rep.passed = passed ? 1 : 0;
+  if (passed) {
+    for (size_t i : comb) res[i] = 1;
+  } else {  // exact verdicts for the combined jobs, one by one
+    const size_t m = comb.size();
+    std::vector<const zkfl_vkey*> fk(m);
+    std::vector<const uint8_t*> fp(m);
+    std::vector<uint8_t> fpr(256 * m);
+    std::vector<int32_t> fres(m, 0);
+    for (size_t j = 0; j < m; j++) {
+      fk[j] = vkeys[comb[j]];
+      fp[j] = pubs[comb[j]];
+      memcpy(fpr.data() + 256 * j, proofs + 256 * comb[j], 256);
+    }
+    rc = verify_multi_run(ctx, m, fk.data(), fp.data(), fpr.data(), fres.data(), ZKFL_VERIFY_AUTO);
+    if (rc != ZKFL_OK) return rc;
+    for (size_t j = 0; j < m; j++) res[comb[j]] = fres[j];
+    rep.fallback = (uint32_t)m;
+  }
+  memcpy(results, res.data(), n * sizeof(int32_t));
+  if (report) *report = rep;
+  return ZKFL_OK;
+}
+
+int zkfl_debug_verify_round(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
+                            const size_t* npubs, const uint8_t* proofs, const uint8_t* z, size_t chunk,
+                            uint8_t gt_out[384], int32_t* screened_out) {
+  if (!ctx || (n && (!vkeys || !pubs || !npubs || !proofs || !z || !gt_out || !screened_out)))
+    return fail(ZKFL_E_ARG, "verify_round: null argument");
+  if (const int rc = verify_jobs_check("verify_round", ctx, n, vkeys, pubs, npubs)) return rc;
+  if (n == 0) return ZKFL_OK;
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  std::vector<int32_t> screened(n, 0);
+  int passed = 0;
+  const int rc = verify_round_combine(ctx, n, vkeys, pubs, proofs, z, chunk, gt_out, screened.data(), &passed, nullptr);
+  if (rc != ZKFL_OK) return rc;
+  memcpy(screened_out, screened.data(), n * sizeof(int32_t));
   return ZKFL_OK;
 }
 

@@ -29,6 +29,9 @@
         paths are taken from the manifest's directory); each distinct vkey is loaded once.  Prints one
         line per job, in job order; exit 0 if all are valid, 1 if any is invalid, 2 on a manifest that
         is not such a list or names a missing file (decided before the GPU is touched)
+        --combined: answer the round by one random combination with one final exponentiation
+        (verify_round; the per-proof path gives the verdicts when it fails).  Same lines and exit
+        codes; the report goes to stderr
 
 <circuit> is one of zkfl.circuits.CIRCUITS (poseidon_hash2, sgd_verified, sgd_step_v5,
 balance_unified, secure_masked_update) followed by its integer template parameters.  GPU
@@ -207,7 +210,12 @@ def cmd_verify_round(args):
         for (vpath, _, _), (vk, _, _) in zip(jobs, data):
             if vpath not in handles:
                 handles[vpath] = p.load_vkey(vk)
-        oks = p.verify_multi([(handles[j[0]], d[1], d[2]) for j, d in zip(jobs, data)])
+        round_jobs = [(handles[j[0]], d[1], d[2]) for j, d in zip(jobs, data)]
+        if args.combined:
+            oks, rep = p.verify_round(round_jobs)
+            print("[INFO]  zkfl: combined round: " + ", ".join(f"{k} {v}" for k, v in rep.items()), file=sys.stderr)
+        else:
+            oks = p.verify_multi(round_jobs)
     finally:
         p.close()
     for i, ok in enumerate(oks):
@@ -259,6 +267,8 @@ def main(argv=None):
         sp.add_argument(a)
     sp = sub.add_parser("verify-round")
     sp.add_argument("round")
+    sp.add_argument("--combined", action="store_true",
+                    help="one random combination and one final exponentiation for the whole round")
     args = ap.parse_args(argv)
     fn = {"compile": cmd_compile, "info": cmd_info, "setup": cmd_setup,
           "r1cs-info": cmd_r1cs_info, "setup-r1cs": cmd_setup_r1cs, "export-vk": cmd_export_vk,

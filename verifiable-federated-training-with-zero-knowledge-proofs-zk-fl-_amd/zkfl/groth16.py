@@ -205,6 +205,14 @@ class Prover:
             [(vk if isinstance(vk, native.VerifyingKey) else self.load_vkey(vk), public_bytes(pub),
               proof_from_json(proof)) for vk, pub, proof in jobs], schedule)
 
+    def verify_round(self, jobs, z=None):
+        """verify_multi's jobs -> ([bool], report dict), answered for the whole round by one random
+        combination with one final exponentiation; when it fails, the exact verdicts come from the
+        per-proof path (Context.verify_round).  z: for tests only."""
+        return self.ctx.verify_round(
+            [(vk if isinstance(vk, native.VerifyingKey) else self.load_vkey(vk), public_bytes(pub),
+              proof_from_json(proof)) for vk, pub, proof in jobs], z)
+
     def close(self):
         for k in list(self._keys.values()) + list(self._vkeys.values()):
             k.close()
@@ -271,6 +279,11 @@ def verify_multi(jobs, schedule: str = "auto") -> list:
     return _prover().verify_multi(jobs, schedule)
 
 
-__all__ = ["prove", "fullProve", "verify", "verify_multi", "load_vkey", "Prover", "proof_to_json", "proof_from_json", "export_verification_key",
+def verify_round(jobs, z=None):
+    """verify_multi's jobs -> ([bool], report dict) by one random combination (Prover.verify_round)."""
+    return _prover().verify_round(jobs, z)
+
+
+__all__ = ["prove", "fullProve", "verify", "verify_multi", "verify_round", "load_vkey", "Prover", "proof_to_json", "proof_from_json", "export_verification_key",
            "vk_bytes", "public_bytes", "wtns_calculate", "r1cs_info", "read_wtns", "wtns_check",
            "wtns_check_report", "zkey_check"]

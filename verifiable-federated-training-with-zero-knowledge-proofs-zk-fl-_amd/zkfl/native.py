@@ -142,7 +142,13 @@ SIGNATURES = {
     "zkfl_vkey_free": (C.c_int, [_P]),
     "zkfl_groth16_verify_multi": (C.c_int, [_P, C.c_size_t, C.POINTER(_P), C.POINTER(C.c_char_p),
                                             C.POINTER(C.c_size_t), C.c_char_p, C.POINTER(C.c_int32), C.c_int]),
-    "zkfl_debug_wave_pairing": (C.c_int, [_P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_int, _U8P]),
+    "zkfl_groth16_verify_round": (C.c_int, [_P, C.c_size_t, C.POINTER(_P), C.POINTER(C.c_char_p),
+                                            C.POINTER(C.c_size_t), C.c_char_p, C.c_char_p, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_uint32)]),
+    "zkfl_debug_verify_round": (C.c_int, [_P, C.c_size_t, C.POINTER(_P), C.POINTER(C.c_char_p),
+                                          C.POINTER(C.c_size_t), C.c_char_p, C.c_char_p, C.c_size_t, _U8P,
+                                          C.POINTER(C.c_int32)]),
+    "zkfl_debug_wave_pairing": (C.c_int,[_P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_int, _U8P]),
     "zkfl_wprog_load": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(_P)]),
     "zkfl_wprog_free": (C.c_int, [_P]),
     "zkfl_wprog_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -495,6 +501,39 @@ class Context(_Handle):
                                               res, sched))
         return [bool(res[i]) for i in range(n)]
 
+    @staticmethod
+    def _round_args(jobs, z):
+        n = len(jobs)
+        for _, public, proof in jobs:
+            assert len(proof) == 256 and len(public) % 32 == 0
+        if z is not None:
+            z = b"".join(int(v).to_bytes(16, "little") for v in z) if not isinstance(z, (bytes, bytearray)) else bytes(z)
+            assert len(z) == 16 * n
+        keys = (_P * max(1, n))(*[k.h for k, _, _ in jobs])
+        pubs = (C.c_char_p * max(1, n))(*[bytes(p) for _, p, _ in jobs])
+        npubs = (C.c_size_t * max(1, n))(*[len(p) // 32 for _, p, _ in jobs])
+        return n, keys, pubs, npubs, b"".join(pr for _, _, pr in jobs), z
+
+    def verify_round(self, jobs, z=None):
+        """verify_multi's jobs and verdicts by one random combination with one final exponentiation
+        (zkfl_groth16_verify_round) -> ([bool] in job order, report dict: keys, screened, combined,
+        passed, fallback).  z (n ints below 2^128, or n x 16 B): for tests only, forfeits soundness;
+        None draws them from the OS CSPRNG inside the call."""
+        n, keys, pubs, npubs, proofs, z = self._round_args(jobs, z)
+        res = (C.c_int32 * max(1, n))()
+        rep = (C.c_uint32 * len(ROUND_REPORT_FIELDS))()
+        check(lib().zkfl_groth16_verify_round(self.h, n, keys, pubs, npubs, proofs, z, res, rep))
+        return [bool(res[i]) for i in range(n)], dict(zip(ROUND_REPORT_FIELDS, (int(v) for v in rep)))
+
+    def debug_verify_round(self, jobs, z, chunk: int = 0):
+        """The parity hook of verify_round -> (the final-exponentiated combination, 384 B in
+        pairing()'s layout; [bool] screened per job).  chunk: proofs per pass (0 = production)."""
+        n, keys, pubs, npubs, proofs, z = self._round_args(jobs, z)
+        out = _buf(384)
+        scr = (C.c_int32 * max(1, n))()
+        check(lib().zkfl_debug_verify_round(self.h, n, keys, pubs, npubs, proofs, z, chunk, out, scr))
+        return bytes(out)[:384], [bool(scr[i]) for i in range(n)]
+
     def wave_pairing(self, g1: bytes, g2: bytes, final_exp: bool = True) -> bytes:
         """pairing() computed by the wave verifier's tower, Miller loop and final exponentiation
         (one pair per wavefront): the parity hook of Context.verify_multi's "waves" schedule."""
@@ -592,6 +631,7 @@ class Context(_Handle):
 
 
 VERIFY_SCHEDULES = {"auto": 0, "lanes": 1, "waves": 2}  # ZKFL_VERIFY_*
+ROUND_REPORT_FIELDS = ("keys", "screened", "combined", "passed", "fallback")  # zkfl_round_report
 
 
 class VerifyingKey(_Handle):
