@@ -134,7 +134,19 @@ int zkfl_debug_ab_partition(const uint8_t* sec_a, const uint8_t* sec_b1, size_t 
  * when its key is unsharded and holds no partition, and learns again (once per call) when more
  * than half of the non-representative wires missed in the key's last proof and the partition was
  * learned; ZKFL_GROUPS=0 (read when the context is made) turns all of it off.  Each build logs
- * its time to stderr. */
+ * its time to stderr.
+ *
+ * Grouped ABC: a key that holds a partition also classes its QAP rows (A and B rows together) by
+ * their terms mapped through rep -- equal multisets of (rep column, coefficient) evaluate alike when
+ * the witness follows -- and keeps one row per class when those hold at most half of the key's
+ * terms.  A proof evaluates the class rows, copies the values to the rows and recomputes from the
+ * original rows the constraints a missing wire touches (the key's per-wire constraint lists); a
+ * wire without a list (more than 256 constraints) that misses, or more than domain / 8 dirty
+ * constraints, sends that proof through the plain ABC.  a, b, c are the same for any partition and
+ * witness.  ZKFL_GROUP_ROWS=0 (read when the context is made) keeps the plain ABC on grouped keys,
+ * and small keys (domain <= 2^ZKFL_SMALL_LOGN) always keep it: their proofs are launch-bound and the
+ * grouped form has three more launches.  zkfl_key_group_rows reports it (a struct of its own, so
+ * zkfl_groups_info keeps its size). */
 typedef struct zkfl_groups_info {
   uint32_t grouped;       /* 1: the key holds a partition */
   uint32_t learned;       /* 1: learned from a witness, 0: set by the caller */
@@ -144,11 +156,23 @@ typedef struct zkfl_groups_info {
   uint32_t bases_rep[4];  /* of them, those that carry a scalar when the witness follows the partition */
   uint32_t builds;        /* partitions built on this key so far */
   uint32_t last_miss;     /* non-zero differences in the key's last finished grouped proof */
-  double build_ms;        /* the last build: host grouping, group sums, expansion */
+  double build_ms;        /* the last build: host grouping, group sums, expansion, row classes */
 } zkfl_groups_info;
+typedef struct zkfl_group_rows_info {
+  uint32_t rows_grouped;/* 1: proofs run the grouped ABC (the class rows hold <= half of the terms) */
+  uint32_t row_classes;   /* classes of equal mapped rows (the empty class included); 0: not built */
+  uint32_t terms;         /* A/B terms of the key (K) */
+  uint32_t terms_rep;     /* terms of one row per class (Kd) */
+  uint32_t wire_list;     /* entries of the non-representative wires' constraint lists */
+  uint32_t wires_over_cap;/* non-representative wires in too many constraints to carry a list */
+  uint32_t last_dirty;    /* constraints recomputed in the key's last finished grouped proof */
+  uint32_t last_plain;    /* 1: that proof ran the plain ABC (a wire over the cap missed, or the list filled) */
+  double rows_build_ms;   /* of build_ms: QAP download, row classes, wire lists, upload */
+} zkfl_group_rows_info;
 int zkfl_key_set_groups(zkfl_key* key, const uint32_t* rep, size_t n_vars);
 int zkfl_key_learn_groups(zkfl_ctx* ctx, zkfl_key* key, const zkfl_witness* w);
 int zkfl_key_groups(const zkfl_key* key, zkfl_groups_info* out);
+int zkfl_key_group_rows(const zkfl_key* key, zkfl_group_rows_info* out);
 /* The host side of it on caller-supplied data (no device): values (n x 32 B, std form) -> rep_out[n]
  * (values NULL: rep_out holds the partition on entry), split by sig (n bytes, nullable), then the
  * grouped form of one query's index map sidx[n_bases] with scalar indices u_base + i:
@@ -157,6 +181,24 @@ int zkfl_key_groups(const zkfl_key* key, zkfl_groups_info* out);
 int zkfl_debug_groups(const uint8_t* values, const uint8_t* sig, size_t n, uint32_t* rep_out, const uint32_t* sidx,
                       size_t n_bases, uint32_t u_base, uint32_t* sidx_out, uint32_t* start_out,
                       uint32_t* members_out);
+/* The host side of the grouped ABC on caller-supplied data (no device): rows[2 domain + 1] (A rows
+ * then B rows over one term array of K = rows[2 domain] terms), cols[K] (packed: column | coefficient
+ * index << cshift; cshift 0: columns, with coefs[K x 8] words), rep[n_vars].  Rows are compared in
+ * full after a match of hash_bits (0..64) bits of their hash, so 0 makes every row collide;
+ * wire_cap 0 = the library's cap.  Out: cls_out[2 domain], crp_out[2 domain + 1], cterms_out[K],
+ * ccoefs_out[K x 8] (cshift 0 only, nullable otherwise), wstart_out[n_vars + 1] (bit 31 of entry i:
+ * wire i is over the cap and carries no list), wlist_out[K], info_out[4] = classes | Kd | wire-list
+ * entries | 1 when Kd <= K / 2 (the grouped ABC is kept). */
+int zkfl_debug_group_rows(const uint32_t* rows, uint32_t domain, const uint32_t* cols, uint32_t cshift,
+                          const uint32_t* coefs, const uint32_t* rep, uint32_t n_vars, uint32_t hash_bits,
+                          uint32_t wire_cap, uint32_t* cls_out, uint32_t* crp_out, uint32_t* cterms_out,
+                          uint32_t* ccoefs_out, uint32_t* wstart_out, uint32_t* wlist_out, uint32_t* info_out);
+/* The ABC stage alone on the key's slot 0, as a proof runs it: abc_out = a | b | c on the domain
+ * (3 x domain x 32 B, std form) for the resident witness w; grouped != 0 runs the form the key's
+ * proofs run (the grouped ABC where the key holds row classes), 0 the plain one.  counts_out[3] =
+ * non-zero differences | dirty constraints | plain flag (zeros in the plain form). */
+int zkfl_debug_abc(zkfl_ctx* ctx, zkfl_key* key, const zkfl_witness* w, int grouped, uint8_t* abc_out,
+                   uint32_t* counts_out);
 /* Number of proofs kept in flight by zkfl_groth16_prove_batch (1..32, default 3).  Each slot
  * owns one HIP stream and its own scratch (~0.6 GB for the 2^18 training circuit); proofs in
  * different slots overlap on the GPU.  HIP maps a process's streams onto GPU_MAX_HW_QUEUES

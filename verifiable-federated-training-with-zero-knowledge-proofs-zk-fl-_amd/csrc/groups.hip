@@ -56,7 +56,7 @@ constexpr int DELTA_T = 256;
 
 __global__ void __launch_bounds__(DELTA_T) k_group_delta(const Fr* __restrict__ w, const uint32_t* __restrict__ rep,
                                                          uint32_t n, Fr* __restrict__ u, uint32_t* __restrict__ cnt,
-                                                         uint32_t* __restrict__ miss_out) {
+                                                         uint32_t* __restrict__ miss_out, const GroupMark M) {
   ZK_LIGHT();
   const uint32_t i = blockIdx.x * DELTA_T + threadIdx.x;
   int nz = 0;
@@ -70,6 +70,20 @@ __global__ void __launch_bounds__(DELTA_T) k_group_delta(const Fr* __restrict__ 
     }
     u[i] = v;
   }
+  if (M.wstart) {
+    // grouped ABC: the missing wires go to the slot's list, one atomic per wave that has any;
+    // k_group_mark walks their constraint lists (or raises the plain flag when there are too many)
+    const unsigned long long m = __ballot(nz);
+    if (m) {
+      const uint32_t lane = threadIdx.x & (warpSize - 1);
+      const int first = __ffsll((long long)m) - 1;
+      uint32_t base = 0;
+      if ((int)lane == first) base = atomicAdd(&M.state[2], (uint32_t)__popcll(m));
+      base = __shfl(base, first);
+      const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      if (nz && at < M.miss_cap) M.missing[at] = i;
+    }
+  }
   const int blk = __syncthreads_count(nz);
   if (threadIdx.x == 0) {
     // the last block to arrive publishes the total and leaves both counters zero for the next launch
@@ -77,8 +91,38 @@ __global__ void __launch_bounds__(DELTA_T) k_group_delta(const Fr* __restrict__ 
     __threadfence();
     if (atomicAdd(&cnt[1], 1u) == gridDim.x - 1) {
       __threadfence();
-      *miss_out = atomicExch(&cnt[0], 0u);
+      miss_out[0] = atomicExch(&cnt[0], 0u);
       cnt[1] = 0;
+    }
+  }
+}
+
+constexpr int MARK_T = 256, MARK_BLOCKS_MAX = 256;
+
+// One wave per missing wire and step, an entry of the wire's list per lane and round: a list of
+// 180 constraints is three rounds of atomics.  Too many missing wires: the plain flag, and no walk.
+__global__ void __launch_bounds__(MARK_T) k_group_mark(const GroupMark M) {
+  ZK_LIGHT();
+  const uint32_t n = M.state[2];
+  if (n == 0) return;
+  if (n > M.miss_cap) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicExch(&M.state[1], 1u);
+    return;
+  }
+  const uint32_t lane = threadIdx.x & (warpSize - 1), per = MARK_T / warpSize;
+  for (uint32_t k = blockIdx.x * per + threadIdx.x / warpSize; k < n; k += gridDim.x * per) {
+    if (__any((int)__atomic_load_n(&M.state[1], __ATOMIC_RELAXED))) return;  // nothing reads the marks now
+    const uint32_t i = M.missing[k], s = M.wstart[i], e = M.wstart[i + 1] & ~GROUP_ROWS_OVER;
+    if (s & GROUP_ROWS_OVER) {
+      if (lane == 0) atomicExch(&M.state[1], 1u);
+      return;
+    }
+    for (uint32_t p = s + lane; p < e; p += warpSize) {
+      const uint32_t j = M.wlist[p], bit = 1u << (j & 31);
+      if (atomicOr(&M.state[GROUP_ROWS_STATE_BITS + (j >> 5)], bit) & bit) continue;
+      const uint32_t at = atomicAdd(&M.state[0], 1u);
+      if (at < M.cap) M.dirty[at] = j;
+      else atomicExch(&M.state[1], 1u);
     }
   }
 }
@@ -96,8 +140,13 @@ template void group_sums<FqOps>(hipStream_t, const G1Aff*, int, size_t, const ui
 template void group_sums<Fq2Ops>(hipStream_t, const G2Aff*, int, size_t, const uint32_t*, const uint32_t*, G2Aff*);
 
 void group_delta(hipStream_t st, const Fr* w, const uint32_t* rep, uint32_t n, Fr* u, uint32_t* cnt,
-                 uint32_t* miss_out) {
-  hipLaunchKernelGGL(k_group_delta, dim3(zk_grid(n, DELTA_T)), dim3(DELTA_T), 0, st, w, rep, n, u, cnt, miss_out);
+                 uint32_t* miss_out, const GroupMark& mark) {
+  hipLaunchKernelGGL(k_group_delta, dim3(zk_grid(n, DELTA_T)), dim3(DELTA_T), 0, st, w, rep, n, u, cnt, miss_out, mark);
+}
+
+void group_mark_rows(hipStream_t st, const GroupMark& mark) {
+  const unsigned blocks = std::min<unsigned>(zk_grid((size_t)mark.miss_cap * 64, MARK_T), MARK_BLOCKS_MAX);
+  hipLaunchKernelGGL(k_group_mark, dim3(blocks), dim3(MARK_T), 0, st, mark);
 }
 
 void key_groups_release(zkfl_key* k) {
@@ -105,7 +154,10 @@ void key_groups_release(zkfl_key* k) {
   msm_bases_free(k->gB1);
   msm_bases_free(k->gB2);
   msm_bases_free(k->gCH);
-  if (k->grp.d_rep) (void)hipFree(k->grp.d_rep);
+  void* ptrs[] = {k->grp.d_rep,    k->grp.d_cls,    k->grp.d_crp,  k->grp.d_cterms,
+                  k->grp.d_ccoefs, k->grp.d_wstart, k->grp.d_wlist};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
   const uint32_t builds = k->grp.builds;
   k->grp = KeyGroups();
   k->grp.builds = builds;
@@ -132,6 +184,59 @@ hipError_t build_query(const MsmBases<F>& plain, MsmBases<F>& out, const GroupQu
   group_sums<F>(st, plain.bases_w, msm_w_of(plain.c), plain.n, d_start, d_members, d_img);
   ZK_CHECK(hipGetLastError());
   return msm_bases_set(out, d_img, q.sidx.data(), extra_start, st, false);
+}
+
+// keys that class their rows: the option on, terms to class, and not a small key (build_rows)
+bool group_rows_wanted(const zkfl_key* k) {
+  return k->ctx->opts.group_rows && k->K != 0 && k->logn > k->ctx->opts.small_logn;
+}
+
+// The key's row classes and wire lists (group_rows_build) under the refined partition rep.  The
+// host image of the QAP is dropped after the load, so the build downloads it: 2 MB of row pointers
+// and 28 MB of packed terms at the training circuit, a few ms once per partition, against holding
+// those 30 MB of host memory per key for as long as the key lives.
+hipError_t build_rows(zkfl_key* k, const std::vector<uint32_t>& rep, hipStream_t st) {
+  KeyGroups& g = k->grp;
+  // Small keys (domain <= 2^SchedOpts::small_logn) keep the plain ABC: their proofs are chains of
+  // latency-bound launches, the ABC is a few microseconds of them, and the grouped form's three
+  // more launches cost config 5 3.6 % (6.3 % weak) when they ran it (profiles/ab_group_rows.log).
+  if (!group_rows_wanted(k)) return hipSuccess;
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint32_t dom = k->n;
+  const size_t K = k->K;
+  std::vector<uint32_t> rows(2 * (size_t)dom + 1), cols(K), coefs;
+  ZK_CHECK(hipMemcpyAsync(rows.data(), k->rows, rows.size() * 4, hipMemcpyDeviceToHost, st));
+  ZK_CHECK(hipMemcpyAsync(cols.data(), k->cols, K * 4, hipMemcpyDeviceToHost, st));
+  if (!k->cshift) {
+    coefs.resize(K * 8);
+    ZK_CHECK(hipMemcpyAsync(coefs.data(), k->coefs, K * 32, hipMemcpyDeviceToHost, st));
+  }
+  ZK_CHECK(hipStreamSynchronize(st));
+  GroupRows R;
+  const uint32_t low = (uint32_t)k->ctx->opts.group_rows_cap;
+  group_rows_build(rows.data(), dom, cols.data(), k->cshift, coefs.data(), rep.data(), k->nVars, 64,
+                   low ? std::min(low, GROUP_ROWS_WIRE_CAP) : GROUP_ROWS_WIRE_CAP, R);
+  g.row_classes = R.classes;
+  g.terms_rep = (uint32_t)R.cterms.size();
+  g.wire_list = (uint32_t)R.wlist.size();
+  g.over_cap = R.over_cap;
+  if (R.keep && !R.cterms.empty()) {
+    auto up = [&](auto*& dst, const std::vector<uint32_t>& v) -> hipError_t {
+      ZK_CHECK(hipMalloc(&dst, (v.size() ? v.size() : 1) * 4));
+      if (!v.empty()) ZK_CHECK(hipMemcpyAsync(dst, v.data(), v.size() * 4, hipMemcpyHostToDevice, st));
+      return hipSuccess;
+    };
+    ZK_CHECK(up(g.d_cls, R.cls));
+    ZK_CHECK(up(g.d_crp, R.crp));
+    ZK_CHECK(up(g.d_cterms, R.cterms));
+    if (!k->cshift) ZK_CHECK(up(g.d_ccoefs, R.ccoefs));
+    ZK_CHECK(up(g.d_wstart, R.wstart));
+    ZK_CHECK(up(g.d_wlist, R.wlist));
+    ZK_CHECK(hipStreamSynchronize(st));
+    g.rows_on = true;
+  }
+  g.rows_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return hipSuccess;
 }
 
 // rep: a valid partition of the key's wires (refined here); builds the grouped sets in place of
@@ -165,6 +270,7 @@ int key_build_groups(zkfl_key* k, std::vector<uint32_t>& rep, bool learned, doub
     if (e == hipSuccess) e = build_query(k->bCH, k->gCH, q[3], X, D, st);
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;
+    if (e == hipSuccess) e = build_rows(k, rep, st);
   }
   if (e != hipSuccess) {
     key_groups_release(k);
@@ -191,6 +297,11 @@ int key_build_groups(zkfl_key* k, std::vector<uint32_t>& rep, bool learned, doub
           "%s and built in %.1f ms\n",
           nV, g.groups, g.non_rep, g.bases[0], g.bases_rep[0], g.bases[1], g.bases_rep[1], g.bases[3], g.bases_rep[3],
           learned ? "learned" : "set", g.build_ms);
+  if (group_rows_wanted(k))
+    fprintf(stderr,
+            "zkfl: key of %u wires: %u row classes, terms %zu -> %u, wire lists %u entries (%u wires over the cap); "
+            "%s ABC, built in %.1f ms of the above\n",
+            nV, g.row_classes, k->K, g.terms_rep, g.wire_list, g.over_cap, g.rows_on ? "grouped" : "plain", g.rows_ms);
   return ZKFL_OK;
 }
 
@@ -255,6 +366,56 @@ int zkfl_key_groups(const zkfl_key* key, zkfl_groups_info* out) {
   out->builds = g.builds;
   out->last_miss = g.last_miss;
   out->build_ms = g.build_ms;
+  return ZKFL_OK;
+}
+
+int zkfl_key_group_rows(const zkfl_key* key, zkfl_group_rows_info* out) {
+  if (!key || !out) return fail(ZKFL_E_ARG, "null argument");
+  const KeyGroups& g = key->grp;
+  *out = zkfl_group_rows_info();
+  out->rows_grouped = g.rows_on;
+  out->row_classes = g.row_classes;
+  out->terms = (uint32_t)key->K;
+  out->terms_rep = g.row_classes ? g.terms_rep : out->terms;
+  out->wire_list = g.wire_list;
+  out->wires_over_cap = g.over_cap;
+  out->last_dirty = g.last_dirty;
+  out->last_plain = g.last_plain;
+  out->rows_build_ms = g.rows_ms;
+  return ZKFL_OK;
+}
+
+int zkfl_debug_group_rows(const uint32_t* rows, uint32_t domain, const uint32_t* cols, uint32_t cshift,
+                          const uint32_t* coefs, const uint32_t* rep, uint32_t n_vars, uint32_t hash_bits,
+                          uint32_t wire_cap, uint32_t* cls_out, uint32_t* crp_out, uint32_t* cterms_out,
+                          uint32_t* ccoefs_out, uint32_t* wstart_out, uint32_t* wlist_out, uint32_t* info_out) {
+  if (!rows || !rep || !cls_out || !crp_out || !cterms_out || !wstart_out || !wlist_out || !info_out ||
+      cshift >= 32 || domain > 0x3FFFFFFFu)
+    return fail(ZKFL_E_ARG, "debug_group_rows: bad arguments");
+  const uint32_t K = rows[2 * (size_t)domain];
+  if (K && (!cols || (!cshift && !coefs))) return fail(ZKFL_E_ARG, "debug_group_rows: terms missing");
+  for (uint32_t r = 0; r < 2 * domain; r++)
+    if (rows[r] > rows[r + 1]) return fail(ZKFL_E_ARG, "debug_group_rows: row pointers must not descend");
+  if (!groups_valid(rep, n_vars)) return fail(ZKFL_E_ARG, "debug_group_rows: not a partition");
+  const uint32_t cmask = cshift ? (1u << cshift) - 1u : 0xFFFFFFFFu;
+  for (uint32_t p = 0; p < K; p++)
+    if ((cols[p] & cmask) >= n_vars) return fail(ZKFL_E_ARG, "debug_group_rows: column past the wires");
+  GroupRows R;
+  group_rows_build(rows, domain, cols, cshift, coefs, rep, n_vars, hash_bits, wire_cap ? wire_cap : GROUP_ROWS_WIRE_CAP,
+                   R);
+  auto put = [](uint32_t* dst, const std::vector<uint32_t>& v) {
+    if (dst && !v.empty()) memcpy(dst, v.data(), v.size() * 4);
+  };
+  put(cls_out, R.cls);
+  put(crp_out, R.crp);
+  put(cterms_out, R.cterms);
+  put(ccoefs_out, R.ccoefs);
+  put(wstart_out, R.wstart);
+  put(wlist_out, R.wlist);
+  info_out[0] = R.classes;
+  info_out[1] = (uint32_t)R.cterms.size();
+  info_out[2] = (uint32_t)R.wlist.size();
+  info_out[3] = R.keep;
   return ZKFL_OK;
 }
 

@@ -52,6 +52,8 @@ struct SchedOpts {
   bool ab_shared = true;  // ZKFL_AB_SHARED: keys load their A query in D form where that has fewer bases
   bool groups = true;     // ZKFL_GROUPS: the grouped form of the witness queries (csrc/groups.h)
   int group_min_batch = 8;  // ZKFL_GROUP_MIN_BATCH: a batch call of at least this many proofs learns a partition
+  bool group_rows = true;   // ZKFL_GROUP_ROWS: a key that holds a partition also classes its QAP rows (grouped ABC)
+  int group_rows_cap = 0;   // ZKFL_GROUP_ROWS_CAP: a lower cap on a wire's constraint list (tests); 0: GROUP_ROWS_WIRE_CAP
 };
 
 struct zkfl_ctx {
@@ -88,14 +90,23 @@ struct ProofSlot {
   Fr* abc_tail = nullptr;
   Fr* h = nullptr;    // [n], then the extra slots
   uint32_t* grp_cnt = nullptr;  // [2] k_group_delta's counters (left zero by every launch)
+  // grouped ABC (csrc/groups.h): the proof's dirty-constraint count | plain flag | one bit per
+  // constraint (zeroed by k_proof_start), the dirty list (group_rows_dirty_cap entries) and the
+  // class values (sized when a proof first needs them: the class count comes with the partition)
+  uint32_t* gr_state = nullptr;
+  uint32_t* gr_dirty = nullptr;
+  uint32_t* gr_missing = nullptr;  // [group_rows_miss_cap] the proof's missing wires (k_group_delta)
+  Fr* cls_val = nullptr;
+  size_t cls_cap = 0;
   zkfl_key* key = nullptr;      // the slot's key
   bool grouped_run = false;     // its in-flight proof runs the grouped form (its miss count is read back)
+  bool rows_run = false;        // ... and the grouped ABC (its dirty count and plain flag are read back)
   G1P* res = nullptr;     // [5]: A', B1', C', H, T
   G2P* resB2 = nullptr;   // [1]
   Fr* d_rs = nullptr;     // r, s (64 B) | GLV halves s1, s2, r1, r2 (4 x 32 B)
   uint32_t* d_parts = nullptr;  // [96]: this rank's part of a split proof (A'|B1'|B2'|C'|H, std affine)
   uint8_t* pinned = nullptr;    // proof (256) | r, s (64) | GLV halves (128) | witness address (8, at
-                                // W_PTR_OFF) | the proof's non-zero u (4, at MISS_OFF) | pad | part (768 at 512)
+                                // W_PTR_OFF) | the proof's non-zero u, dirty constraints, plain flag (3 x 4, at MISS_OFF) | pad | part (768 at 512)
   // side resources (slot_side_resources): A's and B's own sort scratch, so C + H can sort in g1s
   // while B2 still reads B's pairs -- a small key's slots hold them from the start (run_front),
   // any other slot from its first proof alone (run_lowlat), which also makes that schedule's two
@@ -134,6 +145,17 @@ struct KeyGroups {
   uint32_t builds = 0;
   uint32_t last_miss = 0;     // non-zero u of the last finished grouped proof
   uint32_t* d_rep = nullptr;  // [nVars] (device)
+  // grouped ABC (group_rows_build, csrc/groups.h): kept (rows_on) when the classes' rows hold at
+  // most half of the K terms; the device copies of GroupRows
+  bool rows_on = false;
+  uint32_t row_classes = 0;  // D
+  uint32_t terms_rep = 0;    // Kd
+  uint32_t wire_list = 0;    // entries of the wire lists
+  uint32_t over_cap = 0;     // non-representative wires without a list (GROUP_ROWS_WIRE_CAP)
+  double rows_ms = 0;        // QAP download, classes, wire lists, upload (part of build_ms)
+  uint32_t last_dirty = 0, last_plain = 0;  // of the last finished grouped proof
+  uint32_t *d_cls = nullptr, *d_crp = nullptr, *d_cterms = nullptr, *d_wstart = nullptr, *d_wlist = nullptr;
+  Fr* d_ccoefs = nullptr;    // wide terms only
 };
 
 struct zkfl_key {
@@ -221,5 +243,6 @@ int key_reset_graphs(zkfl_key* k);
 // witness d_w (nVars std-form values) and built
 void key_groups_release(zkfl_key* k);
 int key_learn_groups(zkfl_ctx* ctx, zkfl_key* k, const Fr* d_w);
-constexpr size_t MISS_OFF = 456;  // ProofSlot::pinned: the proof's count of non-zero u
+// ProofSlot::pinned: the proof's count of non-zero u, then (grouped ABC) its dirty constraints and plain flag
+constexpr size_t MISS_OFF = 456;
 }  // namespace zkfl

@@ -36,6 +36,10 @@ struct ProofStart {
   const uint64_t* w_src_host;
   uint4* w_dst;
   uint32_t w_nvec;
+  // grouped ABC: the slot's dirty count, plain flag and constraint bits, zeroed for the proof
+  // (gr_words of them; gr_state null: none)
+  uint32_t* gr_state;
+  uint32_t gr_words;
 };
 
 // words of the slot's pinned r | s | GLV halves, copied to the device by k_proof_start
@@ -66,6 +70,28 @@ __device__ __forceinline__ Fr abc_row(const uint32_t* __restrict__ rp, uint32_t 
 void abc_chunks(hipStream_t st, const uint32_t* rp, uint32_t nrows, const AbcTerms& T, const Fr* w, uint32_t K,
                 Fr* head, Fr* tail, Fr* abc);
 void abc_rows(hipStream_t st, const uint32_t* rp, size_t n, uint32_t K, const Fr* head, const Fr* tail, Fr* abc);
+
+// The grouped ABC (csrc/groups.h): one row per class of equal mapped rows, then the dirty
+// constraints again from the original rows.  Both forms are always enqueued and each reads the
+// slot's plain flag on the device, so a captured graph serves a proof that follows the partition
+// and one that does not.
+struct AbcGrouped {
+  const uint32_t* crp;    // [classes + 1] the reduced CSR's row pointers
+  uint32_t classes;
+  AbcTerms terms;         // its Kd terms, in the key's encoding
+  uint32_t Kd;
+  const uint32_t* cls;    // [2n] class of A row j, then of B row j
+  Fr* cls_val;            // [classes] the slot's class values
+  const uint32_t* state;  // the slot's dirty count | plain flag | ... (GroupMark::state)
+  const uint32_t* dirty;  // the slot's dirty list
+  uint32_t cap;           // its capacity
+  uint32_t* report;       // host-coherent: the proof's dirty count and plain flag (k_abc_fix leaves them there)
+};
+// plain flag down: k_abc_chunks over the reduced CSR, a_j = value of class cls[j], b_j = of class
+// cls[n + j], c_j = a_j b_j, then a, b, c of every dirty constraint from the original rows (rp, T,
+// K); plain flag up: k_abc_chunks and k_abc_rows over the original rows
+void abc_grouped(hipStream_t st, const AbcGrouped& G, const uint32_t* rp, size_t n, const AbcTerms& T, const Fr* w,
+                 uint32_t K, Fr* head, Fr* tail, Fr* abc);
 void join_h(hipStream_t st, const Fr* abc, size_t n, Fr* h);
 void proof_start(hipStream_t st, const uint32_t* rs_host, uint32_t* d_rs, Fr* extra, int plain, uint32_t* res3,
                  const ProofStart& ps);

@@ -1,6 +1,8 @@
 // The polynomial stage's kernels (see poly.h).
 #include "poly.h"
 
+#include <algorithm>
+
 #include "common.h"
 #include "msm_api.h"
 #include "wtrace.h"
@@ -17,12 +19,10 @@ namespace {
 // first row segment to head[c], of its last to tail[c], and rows wholly inside the chunk
 // straight to abc[row]; k_abc_rows stitches rows j and n+j and forms c = a*b.
 // (ABC_L and the term encodings, AbcTerms: poly.h)
+// One lane's chunk (the body of k_abc_chunks and of its gated twin below).
 template <bool PACKED>
-__global__ void __launch_bounds__(64) k_abc_chunks(const uint32_t* __restrict__ rp, uint32_t nrows, AbcTerms T,
-                                                   const Fr* __restrict__ w, uint32_t K, Fr* __restrict__ head,
-                                                   Fr* __restrict__ tail, Fr* __restrict__ abc) {
-  ZK_WT(WT_ABC);
-  ZK_LIGHT();
+ZK_DEV void abc_chunk(const uint32_t* __restrict__ rp, uint32_t nrows, const AbcTerms& T, const Fr* __restrict__ w,
+                      uint32_t K, Fr* __restrict__ head, Fr* __restrict__ tail, Fr* __restrict__ abc) {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t p0 = c * ABC_L;
   if (p0 >= K) return;
@@ -80,12 +80,18 @@ __global__ void __launch_bounds__(64) k_abc_chunks(const uint32_t* __restrict__ 
   else tail[c] = acc;
 }
 
-// (abc_row, the row stitching over head / tail / abc: poly.h)
-__global__ void __launch_bounds__(256) k_abc_rows(const uint32_t* __restrict__ rp, size_t n, uint32_t K,
-                                                  const Fr* __restrict__ head, const Fr* __restrict__ tail,
-                                                  Fr* __restrict__ abc) {
-  ZK_WT(WT_ABC_ROWS);
+template <bool PACKED>
+__global__ void __launch_bounds__(64) k_abc_chunks(const uint32_t* __restrict__ rp, uint32_t nrows, AbcTerms T,
+                                                   const Fr* __restrict__ w, uint32_t K, Fr* __restrict__ head,
+                                                   Fr* __restrict__ tail, Fr* __restrict__ abc) {
+  ZK_WT(WT_ABC);
   ZK_LIGHT();
+  abc_chunk<PACKED>(rp, nrows, T, w, K, head, tail, abc);
+}
+
+// (abc_row, the row stitching over head / tail / abc: poly.h)
+ZK_DEV void abc_rows_lane(const uint32_t* __restrict__ rp, size_t n, uint32_t K, const Fr* __restrict__ head,
+                          const Fr* __restrict__ tail, Fr* __restrict__ abc) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const Fr a = abc_row(rp, (uint32_t)j, K, head, tail, abc);
@@ -93,6 +99,108 @@ __global__ void __launch_bounds__(256) k_abc_rows(const uint32_t* __restrict__ r
   abc[j] = a;
   abc[n + j] = b;
   abc[2 * n + j] = fp_mul(a, b);
+}
+
+__global__ void __launch_bounds__(256) k_abc_rows(const uint32_t* __restrict__ rp, size_t n, uint32_t K,
+                                                  const Fr* __restrict__ head, const Fr* __restrict__ tail,
+                                                  Fr* __restrict__ abc) {
+  ZK_WT(WT_ABC_ROWS);
+  ZK_LIGHT();
+  abc_rows_lane(rp, n, K, head, tail, abc);
+}
+
+// ---- The grouped ABC (poly.h AbcGrouped).  Every kernel reads the slot's plain flag state[1]
+// (uniform: one scalar load) and returns at once when the proof runs the other form. ----
+
+// k_abc_chunks and k_abc_rows for a launch that runs only when the plain flag equals `when`: over
+// the reduced CSR (when = 0), or over the original rows (when = 1)
+template <bool PACKED>
+__global__ void __launch_bounds__(64) k_abc_chunks_when(const uint32_t* __restrict__ rp, uint32_t nrows, AbcTerms T,
+                                                        const Fr* __restrict__ w, uint32_t K, Fr* __restrict__ head,
+                                                        Fr* __restrict__ tail, Fr* __restrict__ abc,
+                                                        const uint32_t* __restrict__ state, uint32_t when) {
+  if ((state[1] != 0) != (when != 0)) return;
+  ZK_WT(WT_ABC);
+  ZK_LIGHT();
+  abc_chunk<PACKED>(rp, nrows, T, w, K, head, tail, abc);
+}
+
+__global__ void __launch_bounds__(256) k_abc_rows_plain(const uint32_t* __restrict__ rp, size_t n, uint32_t K,
+                                                        const Fr* __restrict__ head, const Fr* __restrict__ tail,
+                                                        Fr* __restrict__ abc, const uint32_t* __restrict__ state) {
+  if (!state[1]) return;
+  ZK_WT(WT_ABC_ROWS);
+  ZK_LIGHT();
+  abc_rows_lane(rp, n, K, head, tail, abc);
+}
+
+// a_j, b_j = the values of the classes of rows j and n + j, stitched over the reduced CSR's chunks
+__global__ void __launch_bounds__(256) k_abc_rows_grouped(const uint32_t* __restrict__ crp,
+                                                          const uint32_t* __restrict__ cls, size_t n, uint32_t Kd,
+                                                          const Fr* __restrict__ head, const Fr* __restrict__ tail,
+                                                          const Fr* __restrict__ cls_val, Fr* __restrict__ abc,
+                                                          const uint32_t* __restrict__ state) {
+  if (state[1]) return;
+  ZK_WT(WT_ABC_ROWS);
+  ZK_LIGHT();
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const Fr a = abc_row(crp, cls[j], Kd, head, tail, cls_val);
+  const Fr b = abc_row(crp, cls[n + j], Kd, head, tail, cls_val);
+  abc[j] = a;
+  abc[n + j] = b;
+  abc[2 * n + j] = fp_mul(a, b);
+}
+
+// The dirty constraints again, from the original rows: FIX_LANES lanes per constraint stride its A
+// row, then its B row, and fold their sums by butterfly, so a and b of one constraint have one
+// writer (the group's first lane) whichever of its rows a missing wire sits in.
+constexpr int FIX_LANES = 8, FIX_T = 256, FIX_BLOCKS_MAX = 256;
+template <bool PACKED>
+__global__ void __launch_bounds__(FIX_T) k_abc_fix(const uint32_t* __restrict__ rp, AbcTerms T,
+                                                   const Fr* __restrict__ w, size_t n,
+                                                   const uint32_t* __restrict__ state,
+                                                   const uint32_t* __restrict__ dirty, uint32_t cap,
+                                                   Fr* __restrict__ abc, uint32_t* __restrict__ report) {
+  // the marking is complete (stream order): the proof's dirty count and plain flag for the host
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    report[0] = state[0];
+    report[1] = state[1];
+  }
+  if (state[1]) return;
+  ZK_WT(WT_ABC_ROWS);
+  ZK_LIGHT();
+  const uint32_t cnt = state[0] < cap ? state[0] : cap;
+  const uint32_t lane = threadIdx.x % FIX_LANES;
+  const uint32_t cmask = PACKED ? (1u << T.cshift) - 1u : 0xFFFFFFFFu;
+  const uint32_t step = gridDim.x * (FIX_T / FIX_LANES);
+  // d is the same in the FIX_LANES lanes of a group, so a group enters and leaves the loop together
+  for (uint32_t d = (blockIdx.x * FIX_T + threadIdx.x) / FIX_LANES; d < cnt; d += step) {
+    const uint32_t j = dirty[d];
+    Fr ab[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const uint32_t r = h ? (uint32_t)n + j : j, e = rp[r + 1];
+      Fr acc = fp_zero<FrP>();
+      for (uint32_t p = rp[r] + lane; p < e; p += FIX_LANES) {
+        const uint32_t t = T.cols[p];
+        acc = fp_add(acc, fp_mul(PACKED ? T.coefs[t >> T.cshift] : T.coefs[p], w[t & cmask]));
+      }
+#pragma unroll
+      for (int off = FIX_LANES / 2; off; off >>= 1) {
+        Fr o;
+#pragma unroll
+        for (int k = 0; k < 8; k++) o.v[k] = __shfl_xor(acc.v[k], off, FIX_LANES);
+        acc = fp_add(acc, o);
+      }
+      ab[h] = acc;
+    }
+    if (lane == 0) {
+      abc[j] = ab[0];
+      abc[n + j] = ab[1];
+      abc[2 * n + j] = fp_mul(ab[0], ab[1]);
+    }
+  }
 }
 
 // h = a*b - c (coset evaluations), to standard form for the H MSM.
@@ -133,6 +241,9 @@ __global__ void __launch_bounds__(256) k_proof_start(const uint32_t* __restrict_
     for (size_t i = ((size_t)y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; i < ps.w_nvec; i += nb)
       ps.w_dst[i] = src[i];
   }
+  if (y == 0 && ps.gr_state)  // uniform per launch
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < ps.gr_words; i += gridDim.x * blockDim.x)
+      ps.gr_state[i] = 0u;
   if (y == 0 && blockIdx.x == 2 && threadIdx.x < RS_WORDS) d_rs[threadIdx.x] = rs_host[threadIdx.x];
   if (y == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
     const Fr* rs = reinterpret_cast<const Fr*>(rs_host);
@@ -185,6 +296,29 @@ void abc_chunks(hipStream_t st, const uint32_t* rp, uint32_t nrows, const AbcTer
 
 void abc_rows(hipStream_t st, const uint32_t* rp, size_t n, uint32_t K, const Fr* head, const Fr* tail, Fr* abc) {
   hipLaunchKernelGGL(k_abc_rows, dim3(zk_grid(n, 256)), dim3(256), 0, st, rp, n, K, head, tail, abc);
+}
+
+void abc_grouped(hipStream_t st, const AbcGrouped& G, const uint32_t* rp, size_t n, const AbcTerms& T, const Fr* w,
+                 uint32_t K, Fr* head, Fr* tail, Fr* abc) {
+  auto chunks = [&](const uint32_t* rows, uint32_t nrows, const AbcTerms& terms, uint32_t k, Fr* whole, uint32_t when) {
+    const dim3 grid(zk_grid((k + ABC_L - 1) / ABC_L, 64));
+    if (terms.cshift)
+      hipLaunchKernelGGL(k_abc_chunks_when<true>, grid, dim3(64), 0, st, rows, nrows, terms, w, k, head, tail, whole,
+                         G.state, when);
+    else
+      hipLaunchKernelGGL(k_abc_chunks_when<false>, grid, dim3(64), 0, st, rows, nrows, terms, w, k, head, tail, whole,
+                         G.state, when);
+  };
+  chunks(G.crp, G.classes, G.terms, G.Kd, G.cls_val, 0);
+  hipLaunchKernelGGL(k_abc_rows_grouped, dim3(zk_grid(n, 256)), dim3(256), 0, st, G.crp, G.cls, n, G.Kd, head, tail,
+                     G.cls_val, abc, G.state);
+  const dim3 fix_grid(std::min<unsigned>(zk_grid((size_t)G.cap * FIX_LANES, FIX_T), FIX_BLOCKS_MAX));
+  if (T.cshift)
+    hipLaunchKernelGGL(k_abc_fix<true>, fix_grid, dim3(FIX_T), 0, st, rp, T, w, n, G.state, G.dirty, G.cap, abc, G.report);
+  else
+    hipLaunchKernelGGL(k_abc_fix<false>, fix_grid, dim3(FIX_T), 0, st, rp, T, w, n, G.state, G.dirty, G.cap, abc, G.report);
+  chunks(rp, (uint32_t)(2 * n), T, K, abc, 1);
+  hipLaunchKernelGGL(k_abc_rows_plain, dim3(zk_grid(n, 256)), dim3(256), 0, st, rp, n, K, head, tail, abc, G.state);
 }
 
 void join_h(hipStream_t st, const Fr* abc, size_t n, Fr* h) {

@@ -63,7 +63,7 @@ void slot_release(ProofSlot* s) {
   msm_scratch_free(s->g2s);
   msm_tail_free(s->g2t);
   void* ptrs[] = {s->abc, s->abc_head, s->abc_tail, s->h, s->res, s->resB2, s->d_rs, s->d_parts,
-                  s->w_stage, s->grp_cnt};  // extra lives in h
+                  s->w_stage, s->grp_cnt, s->gr_state, s->gr_dirty, s->gr_missing, s->cls_val};  // extra lives in h
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (s->pinned) (void)hipHostFree(s->pinned);
@@ -129,6 +129,12 @@ hipError_t slot_create(zkfl_key* k, ProofSlot** out) {
   s->extra = s->h + n;
   ZK_CHECK(hipMalloc(&s->grp_cnt, 2 * sizeof(uint32_t)));
   ZK_CHECK(hipMemsetAsync(s->grp_cnt, 0, 2 * sizeof(uint32_t), st));
+  // grouped ABC (large keys only: build_rows, csrc/groups.hip): the proof's missing wires and dirty constraints
+  if (may_group && k->ctx->opts.group_rows && k->K && k->logn > k->ctx->opts.small_logn) {
+    ZK_CHECK(hipMalloc(&s->gr_state, group_rows_state_words(n) * sizeof(uint32_t)));
+    ZK_CHECK(hipMalloc(&s->gr_missing, (size_t)group_rows_miss_cap((uint32_t)n) * sizeof(uint32_t)));
+    ZK_CHECK(hipMalloc(&s->gr_dirty, (size_t)group_rows_dirty_cap((uint32_t)n) * sizeof(uint32_t)));
+  }
   s->key = k;
   ZK_CHECK(hipMalloc(&s->abc, n * 3 * 32));
   const size_t abc_chunks = (k->K + ABC_L - 1) / ABC_L + 1;
@@ -294,6 +300,7 @@ struct ProofPlan {
   bool fast_wsum;     // the shorter-chain bucket reduction (msm.h MSM_WSUM_Q_FAST)
   bool graph;         // replayed from the slot's graph (enqueue_proof_graph), witness staged
   bool grouped;       // the key's grouped base sets and the differences u (csrc/groups.h)
+  bool group_rows;    // and its row classes: the grouped ABC (grouped, on a key that kept them)
 };
 
 // The four base sets a plan's proof runs over.
@@ -313,6 +320,7 @@ ProofPlan plan_proof(const SchedOpts& o, const zkfl_key* k, const ProofSlot* s, 
   p.mode = mode;
   // whole proofs on a key that holds a partition (only unsharded keys do) run the grouped sets
   p.grouped = mode == ProofMode::Proof && k->grp.on && !ZK_KNOCKOUT;
+  p.group_rows = p.grouped && k->grp.rows_on && s->gr_state;
   // the latency schedule and graph replay serve whole proofs of the plain build on a key whose B
   // queries share a sort; a serialized profile wants one stream, launch by launch
   const bool plain = mode == ProofMode::Proof && k->share_b && !prof->serialize && !ZK_KNOCKOUT;
@@ -382,21 +390,45 @@ void start(zkfl_key* k, ProofSlot* s, const ProofPlan& p) {
     ps.w_dst = reinterpret_cast<uint4*>(s->w_stage);
     ps.w_nvec = (uint32_t)((size_t)k->nVars * 32 / sizeof(uint4));
   }
+  if (p.group_rows) {  // a replayed graph starts clean after a dirty proof
+    ps.gr_state = s->gr_state;
+    ps.gr_words = (uint32_t)group_rows_state_words(k->n);
+  }
   proof_start(s->st_main, reinterpret_cast<const uint32_t*>(s->pinned + 256), reinterpret_cast<uint32_t*>(s->d_rs),
               s->extra, parts, res3, ps);
 }
 
+// What k_group_delta marks for a plan's proof: the key's wire lists into the slot's state.
+inline GroupMark group_mark(const zkfl_key* k, const ProofSlot* s, const ProofPlan& p) {
+  if (!p.group_rows) return GroupMark{};
+  return {k->grp.d_wstart, k->grp.d_wlist, s->gr_state, s->gr_missing, group_rows_miss_cap(k->n), s->gr_dirty,
+          group_rows_dirty_cap(k->n)};
+}
+
+// Step: a, b, c on the domain (Montgomery form) into the slot's abc, in the plan's form: the
+// grouped ABC reads what start and k_group_delta left in the slot's state.
+void abc_stage(zkfl_key* k, ProofSlot* s, const Fr* d_w, hipStream_t st, const ProofPlan& p) {
+  const size_t n = k->n;
+  const uint32_t K = (uint32_t)k->K;
+  const AbcTerms T = {k->cols, k->coefs, k->cshift};
+  if (p.group_rows) {
+    const KeyGroups& g = k->grp;
+    const AbcTerms R = {g.d_cterms, k->cshift ? k->coefs : g.d_ccoefs, k->cshift};
+    const AbcGrouped G = {g.d_crp, g.row_classes, R, g.terms_rep, g.d_cls, s->cls_val, s->gr_state, s->gr_dirty,
+                          group_rows_dirty_cap(k->n), reinterpret_cast<uint32_t*>(s->pinned + MISS_OFF) + 1};
+    abc_grouped(st, G, k->rows, n, T, d_w, K, s->abc_head, s->abc_tail, s->abc);
+    return;
+  }
+  if (K) abc_chunks(st, k->rows, (uint32_t)(2 * n), T, d_w, K, s->abc_head, s->abc_tail, s->abc);
+  abc_rows(st, k->rows, n, K, s->abc_head, s->abc_tail, s->abc);
+}
+
 // Step: ABC (a, b, c on the domain), the coset NTT of all three and h = a b - c (std form: the H
 // MSM's scalars) on stream st.
-hipError_t abc_ntt(zkfl_key* k, ProofSlot* s, const Fr* d_w, hipStream_t st, Profiler* prof) {
+hipError_t abc_ntt(zkfl_key* k, ProofSlot* s, const Fr* d_w, hipStream_t st, const ProofPlan& p, Profiler* prof) {
   const size_t n = k->n;
   int pi = prof->begin("abc", st);
-  if (k->K) {
-    const uint32_t K = (uint32_t)k->K;
-    const AbcTerms T = {k->cols, k->coefs, k->cshift};
-    abc_chunks(st, k->rows, (uint32_t)(2 * n), T, d_w, K, s->abc_head, s->abc_tail, s->abc);
-  }
-  abc_rows(st, k->rows, n, (uint32_t)k->K, s->abc_head, s->abc_tail, s->abc);
+  abc_stage(k, s, d_w, st, p);
   prof->end(pi, st, (double)k->K);
   pi = prof->begin("ntt", st);
   if (!(ZK_KNOCKOUT & 4)) ZK_CHECK(ntt_coset_shift(k->ntt, s->abc, 3, n, st));
@@ -477,7 +509,7 @@ int run_lowlat(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Pro
   assemble_t(sa, s->res, glv_halves(s), proof_out(s));
   HIP_TRY(hipEventRecord(ev_t, sa), "event");
   // main: ABC / NTT / h, C + H and its tail, then pi_c and pi_b
-  HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
+  HIP_TRY(abc_ntt(k, s, d_w, st, p, prof), "ntt");
   HIP_TRY(msm_accumulate(b.CH, s->g1s, s->g1t[2], W, (const uint32_t*)s->h, st, prof, "msm_accumulate_g1"),
           "msm C+H");
   HIP_TRY(msm_tails(&tails[2], &outs[2], 1, st, p.fast_wsum), "msm tail C+H");
@@ -497,7 +529,7 @@ int run_lowlat(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Pro
 int run_front(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Profiler* prof) {
   hipStream_t st = s->st_main;
   const uint32_t *W = (const uint32_t*)d_w, *E = (const uint32_t*)s->extra;
-  HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
+  HIP_TRY(abc_ntt(k, s, d_w, st, p, prof), "ntt");
   const PlanBases b = plan_bases(k, p);
   const MsmBases<FqOps>* bs[3] = {&b.A, &b.B1, &b.CH};
   MsmScratch<FqOps>* ss[3] = {&s->g1s_a, &s->g1s_b, &s->g1s};
@@ -541,7 +573,7 @@ int run_chain(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Prof
   G2P* o2 = s->resB2;
   if (!p.share_b_sort && !(ZK_KNOCKOUT & 32))
     HIP_TRY(msm_run(b.B2, s->g2s, s->g2t, W, E, s->resB2, st, prof, "msm_accumulate_g2"), "msm B2");
-  if (p.light_first) HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
+  if (p.light_first) HIP_TRY(abc_ntt(k, s, d_w, st, p, prof), "ntt");
   HIP_TRY(msm_accumulate(b.A, sA, s->g1t[0], W, E, st, prof, "msm_accumulate_g1"), "msm A");
   if (p.share_b_sort) {  // B2 right after B1, before C + H reuses the sort scratch
     HIP_TRY(msm_sort(b.B1, sB, s->g1t[1].nnz, W, E, st), "msm B1 sort");
@@ -553,7 +585,7 @@ int run_chain(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Prof
     HIP_TRY(msm_accumulate(b.B1, sB, s->g1t[1], W, E, st, prof, "msm_accumulate_g1"), "msm B1");
   }
   if (parts) HIP_TRY(msm_accumulate(b.CH, s->g1s, s->g1t[2], W, Z, st, prof, "msm_accumulate_g1"), "msm C");
-  if (!p.light_first) HIP_TRY(abc_ntt(k, s, d_w, st, prof), "ntt");
+  if (!p.light_first) HIP_TRY(abc_ntt(k, s, d_w, st, p, prof), "ntt");
   if (parts)
     HIP_TRY(msm_accumulate(b.CH, s->g1s, s->g1t[3], Z, H, st, prof, "msm_accumulate_g1"), "msm H");
   else
@@ -572,10 +604,12 @@ int run_proof(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, const Pro
   const int pp = prof->begin("prove", s->st_main);
   start(k, s, p);
   // the differences u behind the blinding scalars, from the witness the schedule reads (a
-  // graph-replayed proof's stage, just filled by k_proof_start), before any MSM of any stream
+  // graph-replayed proof's stage, just filled by k_proof_start), before any MSM of any stream; with
+  // them the dirty constraints of the grouped ABC, before any schedule reaches its ABC
   if (p.grouped)
     group_delta(s->st_main, d_w, k->grp.d_rep, k->nVars, s->extra + 4, s->grp_cnt,
-                reinterpret_cast<uint32_t*>(s->pinned + MISS_OFF));
+                reinterpret_cast<uint32_t*>(s->pinned + MISS_OFF), group_mark(k, s, p));
+  if (p.group_rows) group_mark_rows(s->st_main, group_mark(k, s, p));
   const int rc = p.schedule == Schedule::Lowlat  ? run_lowlat(k, s, d_w, p, prof)
                  : p.schedule == Schedule::Front ? run_front(k, s, d_w, p, prof)
                                                  : run_chain(k, s, d_w, p, prof);
@@ -619,6 +653,16 @@ int enqueue_proof(zkfl_ctx* ctx, zkfl_key* k, ProofSlot* s, const Fr* d_w, const
   glv_split(rs_host, ks[2], ks[3]);      // r -> r1, r2 (for B1, phi(B1))
   const ProofPlan p = plan_proof(ctx->opts, k, s, mode, batch_of_one, &ctx->prof);
   s->grouped_run = p.grouped;
+  s->rows_run = p.group_rows;
+  // the class values, sized by the partition the key holds now (a new partition drops the slot's
+  // graph, so a captured pointer never outlives its buffer)
+  if (p.group_rows && s->cls_cap < k->grp.row_classes) {
+    if (s->cls_val) (void)hipFree(s->cls_val);
+    s->cls_val = nullptr;
+    s->cls_cap = 0;
+    HIP_TRY(hipMalloc(&s->cls_val, (size_t)k->grp.row_classes * 32), "class values");
+    s->cls_cap = k->grp.row_classes;
+  }
   int rc;
   if (p.graph) {
     // the witness is staged into the slot's own buffer so the captured kernel arguments hold for
@@ -658,7 +702,15 @@ int wait_slot(ProofSlot* s, bool poll = false) {
   HIP_TRY(host_wait(s->ev_done, poll), "sync");
   if (s->out_proof) memcpy(s->out_proof, s->pinned, 256);
   if (s->out_part) memcpy(s->out_part, s->pinned + 512, PART_WORDS * 4);
-  if (s->grouped_run) memcpy(&s->key->grp.last_miss, s->pinned + MISS_OFF, 4);
+  if (s->grouped_run) {
+    uint32_t c[3];
+    memcpy(c, s->pinned + MISS_OFF, sizeof(c));
+    KeyGroups& g = s->key->grp;
+    g.last_miss = c[0];
+    g.last_dirty = s->rows_run ? c[1] : 0;
+    g.last_plain = s->rows_run ? c[2] : 0;
+  }
+  s->rows_run = false;
   s->grouped_run = false;
   s->busy = false;
   return ZKFL_OK;
@@ -1233,6 +1285,50 @@ int zkfl_debug_prove_parts(zkfl_ctx* ctx, zkfl_key* key, const uint8_t* wtns, si
   if (d_o) (void)hipFree(d_o);
   zkfl_witness_free(w);
   return rc;
+}
+
+int zkfl_debug_abc(zkfl_ctx* ctx, zkfl_key* key, const zkfl_witness* w, int grouped, uint8_t* abc_out,
+                   uint32_t* counts_out) {
+  if (!ctx || !key || !w || !abc_out || !counts_out) return fail(ZKFL_E_ARG, "debug_abc: null argument");
+  if (key->ctx != ctx) return fail(ZKFL_E_ARG, "debug_abc: key of another context");
+  if (w->key != key) return fail(ZKFL_E_MISMATCH, "witness uploaded for another key");
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  ProofSlot* s = nullptr;
+  int rc = get_slot(key, 0, &s);
+  if (rc) return rc;
+  if (s->busy && (rc = wait_slot(s))) return rc;
+  // the slot's buffers and the proof's own steps up to ABC: start (which empties the state),
+  // the differences with their marks, the ABC stage of the plan
+  ProofPlan p = {};
+  p.mode = ProofMode::Proof;
+  p.grouped = grouped && key->grp.on;
+  p.group_rows = p.grouped && key->grp.rows_on && s->gr_state;
+  p.share_b_sort = key->share_b;
+  if (p.group_rows && s->cls_cap < key->grp.row_classes) {
+    if (s->cls_val) (void)hipFree(s->cls_val);
+    s->cls_val = nullptr;
+    s->cls_cap = 0;
+    HIP_TRY(hipMalloc(&s->cls_val, (size_t)key->grp.row_classes * 32), "class values");
+    s->cls_cap = key->grp.row_classes;
+  }
+  memset(s->pinned + 256, 0, 64 + 4 * sizeof(GlvScalar));
+  memset(s->pinned + MISS_OFF, 0, 12);
+  hipStream_t st = s->st_main;
+  start(key, s, p);
+  if (p.grouped)
+    group_delta(st, w->d, key->grp.d_rep, key->nVars, s->extra + 4, s->grp_cnt,
+                reinterpret_cast<uint32_t*>(s->pinned + MISS_OFF), group_mark(key, s, p));
+  if (p.group_rows) group_mark_rows(st, group_mark(key, s, p));
+  abc_stage(key, s, w->d, st, p);
+  const size_t n3 = 3 * (size_t)key->n;
+  fr_mont_to_std(st, s->abc, n3);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(abc_out, s->abc, n3 * 32, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return hip_fail(e, "debug abc");
+  memcpy(counts_out, s->pinned + MISS_OFF, 12);
+  if (!p.group_rows) counts_out[1] = counts_out[2] = 0;
+  return ZKFL_OK;
 }
 
 }  // extern "C"

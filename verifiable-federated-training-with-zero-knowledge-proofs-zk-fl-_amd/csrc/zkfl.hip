@@ -248,6 +248,8 @@ int zkfl_ctx_create(int device, zkfl_ctx** out) {
   ctx->opts.ab_shared = env("ZKFL_AB_SHARED", 1) != 0;
   ctx->opts.groups = env("ZKFL_GROUPS", 1) != 0;
   ctx->opts.group_min_batch = std::max(1, env("ZKFL_GROUP_MIN_BATCH", 8));
+  ctx->opts.group_rows = env("ZKFL_GROUP_ROWS", 1) != 0;
+  ctx->opts.group_rows_cap = std::max(0, env("ZKFL_GROUP_ROWS_CAP", 0));
   hipError_t e = hipStreamCreateWithFlags(&ctx->st, hipStreamNonBlocking);
   if (e != hipSuccess) {
     delete ctx;

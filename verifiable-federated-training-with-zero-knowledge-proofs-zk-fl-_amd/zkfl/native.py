@@ -75,6 +75,13 @@ class GroupsInfo(C.Structure):
                 ("last_miss", C.c_uint32), ("build_ms", C.c_double)]
 
 
+class GroupRowsInfo(C.Structure):
+    """zkfl_group_rows_info"""
+    _fields_ = [("rows_grouped", C.c_uint32), ("row_classes", C.c_uint32), ("terms", C.c_uint32),
+                ("terms_rep", C.c_uint32), ("wire_list", C.c_uint32), ("wires_over_cap", C.c_uint32),
+                ("last_dirty", C.c_uint32), ("last_plain", C.c_uint32), ("rows_build_ms", C.c_double)]
+
+
 # every exported symbol of include/zkfl.h with (restype, argtypes)
 SIGNATURES = {
     "zkfl_version": (C.c_int, []),
@@ -104,9 +111,14 @@ SIGNATURES = {
     "zkfl_key_set_groups": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_size_t]),
     "zkfl_key_learn_groups": (C.c_int, [_P, _P, _P]),
     "zkfl_key_groups": (C.c_int, [_P, C.POINTER(GroupsInfo)]),
+    "zkfl_key_group_rows": (C.c_int, [_P, C.POINTER(GroupRowsInfo)]),
     "zkfl_debug_groups": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                     C.c_size_t, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                     C.POINTER(C.c_uint32)]),
+    "zkfl_debug_group_rows": (C.c_int, [C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                                        C.c_uint32] + [C.POINTER(C.c_uint32)] * 7),
+    "zkfl_debug_abc": (C.c_int, [_P, _P, _P, C.c_int, _U8P, C.POINTER(C.c_uint32)]),
     "zkfl_key_set_slots": (C.c_int, [_P, C.c_int]),
     "zkfl_groth16_prove": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, C.c_char_p, _U8P, _U8P,
                                      C.POINTER(C.c_size_t)]),
@@ -710,9 +722,23 @@ class ProvingKey(_Handle):
         non-zero differences of the key's last grouped proof."""
         g = GroupsInfo()
         check(lib().zkfl_key_groups(self.h, C.byref(g)))
+        r = GroupRowsInfo()
+        check(lib().zkfl_key_group_rows(self.h, C.byref(r)))
         return {"grouped": bool(g.grouped), "learned": bool(g.learned), "groups": g.groups, "non_rep": g.non_rep,
                 "bases": dict(zip(GROUP_QUERIES, g.bases)), "bases_rep": dict(zip(GROUP_QUERIES, g.bases_rep)),
-                "builds": g.builds, "last_miss": g.last_miss, "build_ms": g.build_ms}
+                "builds": g.builds, "last_miss": g.last_miss, "build_ms": g.build_ms,
+                # the grouped ABC: row classes, K -> Kd, the wire lists, the last proof's repair
+                "rows_grouped": bool(r.rows_grouped), "row_classes": r.row_classes, "terms": r.terms,
+                "terms_rep": r.terms_rep, "wire_list": r.wire_list, "wires_over_cap": r.wires_over_cap,
+                "last_dirty": r.last_dirty, "last_plain": bool(r.last_plain), "rows_build_ms": r.rows_build_ms}
+
+    def debug_abc(self, w: "ResidentWitness", grouped: bool = True):
+        """The ABC stage alone on slot 0 (zkfl_debug_abc) -> (a | b | c as 3 x domain x 32 B in
+        standard form, non-zero differences, dirty constraints, plain flag)."""
+        out = _buf(96 * self.domain_size)
+        cnt = (C.c_uint32 * 3)()
+        check(lib().zkfl_debug_abc(self.ctx.h, self.h, w.h, 1 if grouped else 0, out, cnt))
+        return bytes(out), cnt[0], cnt[1], bool(cnt[2])
 
     def set_slots(self, slots: int):
         """Proofs kept in flight by prove_batch (each slot = 3 HIP streams + scratch)."""
