@@ -76,7 +76,9 @@ int zkfl_ctx_set_profiling(zkfl_ctx* ctx, int enabled);
  * "verify_wave_inputs", "verify_wave_pair" (the wave verifier's three kernels; units: proofs),
  * "verify_round_screen", "verify_round_pair", "verify_round_reduce", "verify_round_final" (the
  * combined round check's stages; units: proofs),
- * "keycheck_points", "keycheck_rows", "keycheck_msm", "keycheck_pairing" (the key check's stages).
+ * "keycheck_points", "keycheck_rows", "keycheck_msm", "keycheck_pairing" (the key check's stages),
+ * "ptaucheck_points", "ptaucheck_scalars", "ptaucheck_msm", "ptaucheck_pairing" (the ptau check's
+ * stages, one record per chunk pass; units: points).
  * Synchronises the device.
  * total_ms: summed event time; units: summed algorithmic units (MSM entries, NTT elements...);
  * median_ms (nullable): median single-launch time, robust to a one-off stalled dispatch. */
@@ -476,6 +478,86 @@ typedef struct {
 } zkfl_zkey_report;
 int zkfl_zkey_check(zkfl_ctx* ctx, const zkfl_r1cs* r1cs, const uint8_t* zkey, size_t zkey_len,
                     const zkfl_ptau_view* ptau, const uint8_t* rho, const uint8_t* sigma, zkfl_zkey_report* report);
+
+/* Ptau check: is this .ptau a well-formed Powers of Tau for SOME tau, alpha and beta, with sections
+ * 12-15 the Lagrange form of sections 2-5?  `groth16 setup` and the key check above read sections
+ * 12-15 of whatever pot*_final.ptau they are given (tests/full_system_simulation.mjs:677-695), and
+ * the key check reads the same blocks on both sides of its equations: a key made from a ptau whose
+ * Lagrange blocks are not the Lagrange form of its powers, or whose powers are not the powers of one
+ * tau, passes it and is unsound.  This call reads no contribution transcript: it does not establish
+ * who knows tau (snarkjs's `powersoftau verify` asserts that, and is not served here).
+ *
+ * n = 2^power; T, U, A, B = sections 2 (2n-1 points), 3, 4, 5 (n points each), b2 = section 6, points
+ * as the file stores them (mont affine, all-zero = infinity).  Randomness: rho (2n-1 scalars, a
+ * shorter section uses a prefix), z with z^(2n) != 1, gamma_k for the levels k = 0..power+1.  With
+ * S0(X) = sum_{i < len-1} rho_i X[i] and S1(X) = sum_{i < len-1} rho_i X[i+1], in this order:
+ *   STRUCTURE   T[0] == G1, U[0] == G2; T[1], A[0], B[0], b2 are not infinity (host)
+ *   POINTS      every point of sections 2-6 and 12-15 is all-zero or has coordinates < q and lies on
+ *               its curve; G2 points lie in the order-r subgroup
+ *   TAU_G1      e(S0(T), U[1]) == e(S1(T), G2)
+ *   TAU_G2      e(T[1], S0(U)) == e(G1, S1(U))
+ *   ALPHA_G1    e(S0(A), U[1]) == e(S1(A), G2)
+ *   BETA_G1     e(S0(B), U[1]) == e(S1(B), G2)
+ *   BETA_G2     e(B[0], G2) == e(G1, b2)
+ *   L_TAU_G1, L_TAU_G2, L_ALPHA_G1, L_BETA_G1 (section 12 against 2, 13 against 3, 14 against 4, 15
+ *               against 5; no pairing):  MSM(Lagrange section, lam) == MSM(power section, s)
+ * Position p of a Lagrange section lies in level k = bitlength(p+1) - 1 at index j = p + 1 - 2^k;
+ * n_k = 2^k and w_k is the level's domain generator (the one the group iFFT of `prepare phase2`
+ * uses).  Levels run to power+1 for section 12, whose top block was made with the absent power
+ * T[2n-1] as infinity, and to power for the others.
+ *   lam_p = gamma_k w_k^j (z^n_k - 1) / (n_k (z - w_k^j))            = gamma_k L_j^(k) at z
+ *   s_0   = sum_k gamma_k / n_k
+ *   s_i   = z^-i sum_{k : 2^k > i} gamma_k z^n_k / n_k               (i >= 1)
+ * since block k holds (1/n_k) sum_i w_k^(-ij) X[i] and sum_j L_j(z) w_k^(-ij) = z^((n_k - i) mod n_k).
+ * A false accept of a chain check needs a non-zero linear form in rho to vanish at a uniform point
+ * (<= 2^-253); of a Lagrange check, a non-zero linear form in gamma (<= 2^-253) or a non-zero
+ * polynomial of degree < 2n in z (<= 2n / r < 2^-224 at power 28).
+ *
+ * Every section goes through the device in chunks of at most chunk_points points (0: the default,
+ * 2^20), so device memory is bounded by the chunk and the file may be a mapped image of any size.
+ * A section with a bad point takes no part in the later checks, which then read
+ * ZKFL_PTAUCHECK_NOT_RUN; an unprepared file (no sections 12-15) runs the first seven checks, the
+ * Lagrange checks read NOT_RUN, prepared = 0 and the call returns ZKFL_OK when the seven hold.
+ *
+ * zkfl_ptau_parse validates the layout alone (iden3 binfile "ptau" v1, bn128, power 1..28, every
+ * section's byte count, sections 12-15 all present or all absent; ZKFL_E_FORMAT / ZKFL_E_PRIME /
+ * ZKFL_E_MISMATCH) and needs no device.
+ * rnd: z | gamma[power+2] | rho[2n-1], 32 B std form each, or NULL to draw them from the OS CSPRNG
+ * (z redrawn until z^(2n) != 1).  Non-NULL values are for tests and forfeit soundness.  A given
+ * scalar >= r or a z on the domain gives ZKFL_E_ARG, a malformed file the parser's codes -- all
+ * before any device work.  Returns ZKFL_OK when every check that ran holds, ZKFL_E_KEY when one
+ * fails (zkfl_last_error names the first in the order above and, for points, section and index;
+ * the report is filled).
+ * zkfl_ptau_report: status[] per check (ZKFL_KEYCHECK_PASS / _FAIL / _NOT_RUN's values); point_* =
+ * the first section in file order with a bad point, its lowest bad index and how many of its points
+ * are bad; chunks = the chunk passes that ran. */
+#define ZKFL_PTAUCHECK_STRUCTURE 0
+#define ZKFL_PTAUCHECK_POINTS 1
+#define ZKFL_PTAUCHECK_TAU_G1 2
+#define ZKFL_PTAUCHECK_TAU_G2 3
+#define ZKFL_PTAUCHECK_ALPHA_G1 4
+#define ZKFL_PTAUCHECK_BETA_G1 5
+#define ZKFL_PTAUCHECK_BETA_G2 6
+#define ZKFL_PTAUCHECK_L_TAU_G1 7
+#define ZKFL_PTAUCHECK_L_TAU_G2 8
+#define ZKFL_PTAUCHECK_L_ALPHA_G1 9
+#define ZKFL_PTAUCHECK_L_BETA_G1 10
+#define ZKFL_PTAUCHECK_N 11
+#define ZKFL_PTAUCHECK_PASS 0
+#define ZKFL_PTAUCHECK_FAIL 1
+#define ZKFL_PTAUCHECK_NOT_RUN 2
+typedef struct {
+  uint32_t power, ceremony_power, prepared, contributions;
+} zkfl_ptau_header;
+typedef struct {
+  uint32_t status[ZKFL_PTAUCHECK_N];
+  uint32_t prepared, power;
+  uint32_t point_section, point_index, point_count;
+  uint32_t chunks;
+} zkfl_ptau_report;
+int zkfl_ptau_parse(const uint8_t* buf, size_t len, zkfl_ptau_header* out);
+int zkfl_ptau_check(zkfl_ctx* ctx, const uint8_t* ptau, size_t len, const uint8_t* rnd, uint32_t chunk_points,
+                    zkfl_ptau_report* report);
 
 /* Verification (replaces `snarkjs groth16 verify <vkey> <public> <proof>`,
  * tests/full_system_simulation.mjs:865-868; snarkjs groth16_verify, restated in

@@ -3,6 +3,7 @@
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -I include -I <pkg>/csrc tools/parse_fuzz.cc <pkg>/csrc/host_parse.cc -o parse_fuzz
 //   parse_fuzz <zkey> <wtns> <wprog image> <input.json>
+//   parse_fuzz --ptau <pot.ptau>        the .ptau parser alone (zkfl_ptau_parse / zkfl_ptau_check)
 // Each well-formed file must parse; then every parser meets every prefix of its file (all of them
 // for short files, a strided set plus the header region for long ones), byte flips over the header
 // region, every 32/64-bit field of the binfile section table overwritten with hostile sizes
@@ -93,9 +94,41 @@ static void mutate_binary(const std::vector<uint8_t>& file, bool binfile, F fn) 
   }
 }
 
+// The .ptau parser: the corpus file must parse, and what it returns must lie inside the image.
+static int ptau_target(const char* path) {
+  const std::vector<uint8_t> pt = slurp(path);
+  if (pt.empty()) {
+    fprintf(stderr, "unreadable corpus file\n");
+    return 2;
+  }
+  auto ptau = [](const uint8_t* b, size_t l) {
+    PtauHost p;
+    std::string e;
+    const int rc = ptau_parse(b, l, p, e);
+    if (rc == 0) {  // touch the first and last byte of every section it hands out
+      volatile uint8_t sink = 0;
+      for (int t = 0; t < 16; t++)
+        if (p.sec[t] && p.cnt[t]) {
+          const size_t psz = (t == 3 || t == 6 || t == 13) ? 128 : 64;
+          sink = sink + p.sec[t][0] + p.sec[t][p.cnt[t] * psz - 1];
+        }
+      (void)sink;
+    }
+    return rc;
+  };
+  if (run_on(pt, pt.size(), ptau)) {
+    fprintf(stderr, "corpus file rejected\n");
+    return 3;
+  }
+  mutate_binary(pt, true, ptau);
+  printf("parse_fuzz: %zu cases, no sanitizer findings\n", g_cases);
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc == 3 && strcmp(argv[1], "--ptau") == 0) return ptau_target(argv[2]);
   if (argc != 5) {
-    fprintf(stderr, "usage: %s <zkey> <wtns> <wprog image> <input.json>\n", argv[0]);
+    fprintf(stderr, "usage: %s <zkey> <wtns> <wprog image> <input.json>\n       %s --ptau <pot.ptau>\n", argv[0], argv[0]);
     return 2;
   }
   const std::vector<uint8_t> zk = slurp(argv[1]), wt = slurp(argv[2]), wp = slurp(argv[3]), js = slurp(argv[4]);

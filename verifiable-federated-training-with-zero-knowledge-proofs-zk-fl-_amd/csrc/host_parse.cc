@@ -518,6 +518,46 @@ int zkey_parse(const uint8_t* buf, size_t len, ZkeyHost& z, std::string& err) {
   return coef_csr(cs + 4, ncoef, z, err);
 }
 
+// .ptau: the header and every section's byte count against the power (zkfl/ptau.py::Ptau's rules).
+// The counts are at most 2^30 points, so count * size cannot wrap a size_t.
+int ptau_parse(const uint8_t* buf, size_t len, PtauHost& o, std::string& err) {
+  std::vector<Section> s;
+  int rc = binfile_sections(buf, len, "ptau", s, err);
+  if (rc) return rc;
+  if (rd32(buf + 4) != 1) return bad(err, ZKFL_E_FORMAT, "ptau: unsupported version");
+  for (int t = 1; t <= 7; t++)
+    if (!s[t].present) return bad(err, ZKFL_E_FORMAT, "ptau: missing section " + std::to_string(t));
+  if (s[1].size < 4 + 32 + 8) return bad(err, ZKFL_E_FORMAT, "ptau: header section too short");
+  const uint8_t* h = buf + s[1].off;
+  if (rd32(h) != 32 || memcmp(h + 4, Q_LIMBS, 32) != 0) return bad(err, ZKFL_E_PRIME, "ptau: curve is not bn128 (BN254)");
+  o.power = rd32(h + 36);
+  o.ceremony_power = rd32(h + 40);
+  if (o.power < 1 || o.power > 28) return bad(err, ZKFL_E_FORMAT, "ptau: power " + std::to_string(o.power) + " out of range");
+  const size_t n = (size_t)1 << o.power;
+  int present = 0;
+  for (int t = 12; t <= 15; t++) present += s[t].present ? 1 : 0;
+  if (present != 0 && present != 4) return bad(err, ZKFL_E_FORMAT, "ptau: sections 12-15 are not all present or all absent");
+  o.prepared = present == 4;
+  for (int t = 0; t < 16; t++) {
+    o.sec[t] = nullptr;
+    o.cnt[t] = 0;
+  }
+  const size_t counts[16] = {0, 0, 2 * n - 1, n, n, n, 1, 0, 0, 0, 0, 0, 4 * n - 1, 2 * n - 1, 2 * n - 1, 2 * n - 1};
+  for (int t = 2; t <= 15; t++) {
+    if (!counts[t] || (t >= 12 && !o.prepared)) continue;
+    const size_t psz = (t == 3 || t == 6 || t == 13) ? 128 : 64;
+    if (s[t].size != counts[t] * psz)
+      return bad(err, ZKFL_E_MISMATCH,
+                 "ptau: section " + std::to_string(t) + " holds " + std::to_string(s[t].size) + " bytes, expected " +
+                     std::to_string(counts[t] * psz));
+    o.sec[t] = buf + s[t].off;
+    o.cnt[t] = counts[t];
+  }
+  if (s[7].size < 4) return bad(err, ZKFL_E_FORMAT, "ptau: contributions section");
+  o.contributions = rd32(buf + s[7].off);
+  return ZKFL_OK;
+}
+
 // .r1cs: one validating walk over section 2 that counts each row's terms, then (csr) a second
 // walk that scatters them -- the file interleaves A_j, B_j, C_j, the rows are grouped by matrix.
 int r1cs_parse(const uint8_t* buf, size_t len, bool csr, R1csHost& o, std::string& err) {

@@ -87,6 +87,19 @@ struct R1csHost {
 };
 int r1cs_parse(const uint8_t* buf, size_t len, bool csr, R1csHost& out, std::string& err);
 
+// snarkjs .ptau v1 (the layout zkfl/ptau.py documents; it rejects what its Ptau class rejects):
+// sections 1-7 present, bn128's q, power 1..28, sections 2-6 of 2n-1 / n / n / n / 1 points
+// (n = 2^power; G1 64 B, G2 128 B), sections 12-15 all present -- of 4n-1 / 2n-1 / 2n-1 / 2n-1
+// points -- or all absent.  sec[t] / cnt[t]: section t's first byte and its point count (t = 2..6,
+// 12..15; null / 0 for the Lagrange sections of an unprepared file).
+struct PtauHost {
+  uint32_t power = 0, ceremony_power = 0, contributions = 0;
+  bool prepared = false;
+  const uint8_t* sec[16] = {};
+  size_t cnt[16] = {};
+};
+int ptau_parse(const uint8_t* buf, size_t len, PtauHost& out, std::string& err);
+
 // ---------------------------------------------------------------------------
 // Witness-program image (zkfl/wprog.py, "zkwp" v2)
 // ---------------------------------------------------------------------------

@@ -14,14 +14,6 @@
 //            scalars device-resident (the rows to std form in place), each block uploaded once;
 //   pairing  k_key_finish compares the G1 / G2 sums of A, B1, B2 and writes the eight pairing
 //            inputs, which go through verify.h pairing_batch; the GT values are compared pairwise.
+// The point test, the verdict reduction and the comparison helpers are pointcheck.h's (shared with
+// the ptau check).
 #pragma once
-#include <stdint.h>
-
-namespace zkfl {
-
-// a counted verdict as the device leaves it: how many items failed and the lowest of them
-struct KeyVerdict {
-  uint32_t n_bad, first;
-};
-
-}  // namespace zkfl

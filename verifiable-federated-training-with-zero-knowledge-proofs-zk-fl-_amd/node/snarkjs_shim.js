@@ -279,8 +279,24 @@ function zkeyCheck(r1csFile, ptauFile, zkeyFile) {
   });
 }
 
+// powersOfTau.check(ptauFileName) -> true / false: is the file a well-formed Powers of Tau for some
+// tau, alpha and beta, with sections 12-15 the Lagrange form of sections 2-5 (an unprepared file
+// passes on its powers alone)?  The Python host's `powersoftau check` (libzkfl zkfl_ptau_check) as a
+// child process, its report on this process's stderr.  Not a snarkjs call: snarkjs's
+// powersOfTau.verify asserts the contribution transcript, which this does not read.
+function ptauCheck(ptauFile) {
+  return new Promise((resolve, reject) => {
+    const c = require('child_process').spawn(process.env.ZKFL_PYTHON || 'python3',
+      ['-m', 'zkfl', 'powersoftau', 'check', ptauFile], { stdio: ['ignore', 'ignore', 'inherit'], env: hostEnv() });
+    c.on('error', reject);
+    c.on('exit', (code) => (code === 0 || code === 1 ? resolve(code === 0)
+      : reject(new Error('powersoftau check: the zkfl host exited with status ' + code))));
+  });
+}
+
 module.exports = {
   groth16: { prove, fullProve, verify },
+  powersOfTau: { check: ptauCheck },
   wtns: { calculate: wtnsCalculate, check: wtnsCheck },
   zKey: { exportVerificationKey, check: zkeyCheck },
   r1cs: { info: r1csInfo },
@@ -310,7 +326,9 @@ function done(p) {
 // GPU): `python3 -m zkfl <the same argv>` as a child process, its exit status passed through.
 // `wtns check <c.r1cs> <w.wtns>` (alias wchk) goes the same way: the addon has no binding of its own.
 // So does `zkey check <c.r1cs> <pot.ptau> <c.zkey>` (libzkfl zkfl_zkey_check; not a snarkjs command:
-// `zkey verify` asserts a contribution transcript and stays unserved).
+// `zkey verify` asserts a contribution transcript and stays unserved), and `powersoftau check
+// <pot.ptau>` (libzkfl zkfl_ptau_check), which the `powersoftau` verb already routes there;
+// `powersoftau verify` / `ptv` assert the contribution transcript and stay unserved.
 const CEREMONY = new Set(['powersoftau', 'ptn', 'ptc', 'pt2', 'g16s', 'zkn', 'zkc', 'wchk']);
 
 function isCeremony(argv) {
@@ -390,7 +408,10 @@ if (require.main === module && isCeremony(process.argv.slice(2))) {
                   '       snarkjs powersoftau prepare phase2 <in.ptau> <out.ptau>\n' +
                   '       snarkjs groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>\n' +
                   '       snarkjs zkey contribute <in.zkey> <out.zkey> [--name=name] [-e=entropy]\n' +
-                  '       snarkjs zkey check <circuit.r1cs> <pot_final.ptau> <circuit.zkey>');
+                  '       snarkjs zkey check <circuit.r1cs> <pot_final.ptau> <circuit.zkey> [--check-ptau]\n' +
+                  '       snarkjs powersoftau check <pot.ptau>\n' +
+                  '  (powersoftau verify / ptv are not served: they assert the contribution transcript, which\n' +
+                  '   powersoftau check does not read)');
     process.exit(99);
   }
 }

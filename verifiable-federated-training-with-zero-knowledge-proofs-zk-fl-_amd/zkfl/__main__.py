@@ -22,7 +22,11 @@
         --check-key <circuit.r1cs> <pot_final.ptau>: check the key first (as `zkey check`), the same way
     python -m zkfl zkey check <circuit.r1cs> <pot_final.ptau> <circuit.zkey>   is the key the circuit's Groth16 key over
         that prepared ptau, for some delta?  One line per check; exit 0, 1 when a check fails, 2 on
-        unusable arguments (the reference trusts any `<c>_final.zkey` it finds, :713-738)
+        unusable arguments (the reference trusts any `<c>_final.zkey` it finds, :713-738); --check-ptau:
+        the ptau check below first
+    python -m zkfl powersoftau check <pot.ptau>      is the file a well-formed Powers of Tau for some tau, alpha and
+        beta, with sections 12-15 the Lagrange form of sections 2-5 (the reference takes any pot*_final.ptau
+        it finds, :677-695)?  The same exit codes; an unprepared file passes on its powers alone
     python -m zkfl verify <vkey.json> <public.json> <proof.json>            snarkjs groth16 verify (:865-868)
     python -m zkfl verify-round <round.json>                 a round's `groth16 verify` calls (:1298-1343) as one
         verify_multi call.  round.json: a list of {"vkey": path, "public": path, "proof": path} (relative

@@ -9,6 +9,7 @@ Mirrors the snarkjs API/CLI the reference harness drives:
   ``verify(vkey, public, proof)``          <- ``snarkjs groth16 verify`` (:865-868), on the GPU
   ``wtns_check(r1cs, wtns)``               <- ``snarkjs wtns check <c.r1cs> <w.wtns>`` (snarkjs ``wtns.check``), on the GPU
   ``zkey_check(r1cs, ptau, zkey)``         the key against its circuit and ptau (no snarkjs counterpart), on the GPU
+  ``ptau_check(ptau)``                     the ptau's powers and Lagrange sections (no transcript: not ``powersoftau verify``), on the GPU
 Outputs are snarkjs's JSON shapes: proof.json = {pi_a, pi_b, pi_c, protocol, curve} with
 decimal strings, public.json = list of decimal strings (witness[1..nPublic]).
 """
@@ -252,12 +253,22 @@ def wtns_check(r1cs, wtns, ctx: native.Context | None = None) -> bool:
     return wtns_check_report(r1cs, wtns, ctx).ok
 
 
-def zkey_check(r1cs, ptau, zkey, ctx: native.Context | None = None) -> native.KeyReport:
+def zkey_check(r1cs, ptau, zkey, ctx: native.Context | None = None, check_ptau: bool = False):
     """Is ``zkey`` the Groth16 proving key of ``r1cs`` over the prepared ``ptau`` (bytes or paths),
     for some delta and gamma?  -> the report (``.ok``, ``.checks``, ``.error``), checked on the GPU
-    (zkfl/keycheck.py).  No snarkjs counterpart: ``zkey verify`` asserts a contribution transcript."""
+    (zkfl/keycheck.py).  No snarkjs counterpart: ``zkey verify`` asserts a contribution transcript.
+    check_ptau: run ``ptau_check`` on the ptau first and stop with its report if it fails."""
     from . import keycheck
-    return keycheck.zkey_check(r1cs, ptau, zkey, ctx or _prover().ctx)
+    return keycheck.zkey_check(r1cs, ptau, zkey, ctx or _prover().ctx, check_ptau=check_ptau)
+
+
+def ptau_check(ptau, ctx: native.Context | None = None) -> native.PtauReport:
+    """Is ``ptau`` (bytes, or a path, which is mapped) a well-formed Powers of Tau for some tau,
+    alpha and beta, with sections 12-15 the Lagrange form of sections 2-5?  -> the report (``.ok``,
+    ``.checks``, ``.prepared``, ``.error``), checked on the GPU (zkfl/ptaucheck.py).  It reads no
+    contribution transcript: not ``powersoftau verify``."""
+    from . import ptaucheck
+    return ptaucheck.ptau_check(ptau, ctx or _prover().ctx)
 
 
 def fullProve(inputs: dict, circuit, zkey, rs: bytes | None = None):  # noqa: N802 (snarkjs name)
@@ -286,4 +297,4 @@ def verify_round(jobs, z=None):
 
 __all__ = ["prove", "fullProve", "verify", "verify_multi", "verify_round", "load_vkey", "Prover", "proof_to_json", "proof_from_json", "export_verification_key",
            "vk_bytes", "public_bytes", "wtns_calculate", "r1cs_info", "read_wtns", "wtns_check",
-           "wtns_check_report", "zkey_check"]
+           "wtns_check_report", "zkey_check", "ptau_check"]

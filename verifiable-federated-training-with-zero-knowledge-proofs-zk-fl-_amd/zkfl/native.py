@@ -65,6 +65,28 @@ class ZkeyReport(C.Structure):
                 ("coef_matrix", C.c_uint32), ("coef_row", C.c_uint32), ("coef_count", C.c_uint32)]
 
 
+# zkfl_ptau_check's checks in the order they are reported (their states are KEY_STATES)
+PTAU_CHECKS = ("STRUCTURE", "POINTS", "TAU_G1", "TAU_G2", "ALPHA_G1", "BETA_G1", "BETA_G2",
+               "L_TAU_G1", "L_TAU_G2", "L_ALPHA_G1", "L_BETA_G1")
+PTAU_LAGRANGE_CHECKS = PTAU_CHECKS[7:]
+
+
+class PtauHeader(C.Structure):
+    """zkfl_ptau_header"""
+    _fields_ = [("power", C.c_uint32), ("ceremony_power", C.c_uint32), ("prepared", C.c_uint32),
+                ("contributions", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class PtauReportC(C.Structure):
+    """zkfl_ptau_report"""
+    _fields_ = [("status", C.c_uint32 * len(PTAU_CHECKS)), ("prepared", C.c_uint32), ("power", C.c_uint32),
+                ("point_section", C.c_uint32), ("point_index", C.c_uint32), ("point_count", C.c_uint32),
+                ("chunks", C.c_uint32)]
+
+
 GROUP_QUERIES = ("A", "B1", "B2", "CH")
 
 
@@ -191,6 +213,8 @@ SIGNATURES = {
     "zkfl_r1cs_check_resident": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(_P), C.POINTER(R1csReport)]),
     "zkfl_zkey_check": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, C.POINTER(PtauView), C.c_char_p, C.c_char_p,
                                   C.POINTER(ZkeyReport)]),
+    "zkfl_ptau_parse": (C.c_int, [_P, C.c_size_t, C.POINTER(PtauHeader)]),
+    "zkfl_ptau_check": (C.c_int, [_P, _P, C.c_size_t, C.c_char_p, C.c_uint32, C.POINTER(PtauReportC)]),
 }
 
 
@@ -360,6 +384,20 @@ class Context(_Handle):
 
     def synchronize(self):
         check(lib().zkfl_ctx_synchronize(self.h))
+
+    def check_ptau(self, buf, rnd: bytes | None = None, chunk_points: int = 0) -> "PtauReport":
+        """zkfl_ptau_check: is ``buf`` (bytes, or any buffer such as a mapped file) a well-formed
+        Powers of Tau with sections 12-15 the Lagrange form of sections 2-5?  rnd: None draws the
+        scalars from the OS CSPRNG; bytes (z | gamma[power + 2] | rho[2n - 1], 32 B std each) are for
+        tests and forfeit soundness.  chunk_points: points per device pass (0: the library's
+        default).  -> PtauReport; unusable arguments or a malformed file raise ZkflError."""
+        addr, length, keep = _buffer_address(buf)
+        rep = PtauReportC()
+        rc = lib().zkfl_ptau_check(self.h, addr, length, rnd, chunk_points, C.byref(rep))
+        del keep
+        if rc not in (ZKFL_OK, -8):
+            check(rc)
+        return PtauReport(rc, rep, lib().zkfl_last_error().decode(errors="replace") if rc else "")
 
     # wave timeline (libraries built with -DZK_WTRACE=1; tools/wtrace.py)
     def wtrace_start(self, cap: int):
@@ -907,6 +945,70 @@ class Report:
         if self.ok:
             return "Report(ok)"
         return f"Report(n_failed={self.n_failed}, first={self.first}, a={self.a}, b={self.b}, c={self.c})"
+
+
+def _buffer_address(buf):
+    """(address, length, an object to keep alive) of a bytes-like object, without copying it: bytes
+    go through a char pointer, anything else (a bytearray, a read-only or writable mmap) through
+    the buffer protocol."""
+    if isinstance(buf, bytes):
+        return C.cast(C.c_char_p(buf), _P), len(buf), buf
+    mv = memoryview(buf)
+    if not mv.contiguous:
+        raise ValueError("buffer is not contiguous")
+    if mv.readonly:
+        # ctypes.from_buffer needs a writable buffer; numpy takes the address of a read-only one
+        import numpy as np
+        arr = np.frombuffer(mv, dtype=np.uint8)
+        return _P(arr.ctypes.data), arr.nbytes, (arr, mv)
+    arr = (C.c_uint8 * mv.nbytes).from_buffer(mv)
+    return C.cast(arr, _P), mv.nbytes, (arr, mv)
+
+
+def ptau_header(buf) -> dict:
+    """A .ptau's layout validated and its header (zkfl_ptau_parse; host only, no device)."""
+    addr, length, keep = _buffer_address(buf)
+    h = PtauHeader()
+    rc = lib().zkfl_ptau_parse(addr, length, C.byref(h))
+    del keep
+    check(rc)
+    return h.as_dict()
+
+
+class PtauReport:
+    """One ptau check: ``checks`` maps each of PTAU_CHECKS to "pass" / "fail" / "not run";
+    ``prepared``, ``power``; ``point`` = (section, lowest bad index, count) when the points check
+    fails; ``chunks`` = the chunk passes that ran; ``error`` = the library's message naming the
+    first failing check."""
+
+    def __init__(self, rc: int, rep: PtauReportC, error: str):
+        self.rc = rc
+        self.ok = rc == ZKFL_OK
+        self.error = error
+        self.status = [int(x) for x in rep.status]
+        self.checks = {name: KEY_STATES[rep.status[i]] for i, name in enumerate(PTAU_CHECKS)}
+        self.failed = [name for name in PTAU_CHECKS if self.checks[name] == "fail"]
+        self.first_failed = self.failed[0] if self.failed else None
+        self.prepared = bool(rep.prepared)
+        self.power = int(rep.power)
+        self.chunks = int(rep.chunks)
+        self.point = ((rep.point_section, rep.point_index, rep.point_count)
+                      if self.checks["POINTS"] == "fail" else None)
+
+    def lines(self) -> list:
+        """One line per check, as `powersoftau check` prints them."""
+        out = []
+        for name in PTAU_CHECKS:
+            line = f"{name}: {self.checks[name]}"
+            if name == "POINTS" and self.point:
+                line += f" (section {self.point[0]}, point {self.point[1]}, {self.point[2]} bad)"
+            if name in PTAU_LAGRANGE_CHECKS and not self.prepared:
+                line += " (not prepared)"
+            out.append(line)
+        return out
+
+    def __repr__(self):
+        return f"PtauReport({'ok' if self.ok else self.error})"
 
 
 def r1cs_header(r1cs: bytes) -> dict:

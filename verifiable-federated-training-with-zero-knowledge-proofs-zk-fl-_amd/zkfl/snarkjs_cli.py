@@ -12,6 +12,10 @@ Served for `python -m zkfl <snarkjs argv>` and, through it, for the Node shim's 
   zkey check <c.r1cs> <pot.ptau> <c.zkey>             the key check (zkfl/keycheck.py; not a snarkjs command:
                                                       `zkey verify` / `zkv` assert a contribution transcript,
                                                       which this does not test, and stay unserved)
+  powersoftau check <pot.ptau>                        the ptau check (zkfl/ptaucheck.py; not a snarkjs command:
+                                                      `powersoftau verify` / `ptv` assert the contribution
+                                                      transcript, which this does not read and this framework's
+                                                      dev records do not carry, and stay unserved)
 and the snarkjs aliases ptn, ptc, pt2, g16s, zkn (= groth16 setup), zkc, zkev.  The group work runs
 on the GPU (zkfl/ptau.py, zkfl/zkey.py -> libzkfl zkfl_setup_*).  Exit status 0 on success, 1 with
 an `[ERROR] snarkJS: ...` line otherwise (snarkjs's CLI convention).
@@ -108,7 +112,15 @@ def run(argv) -> int:
     pos, opts = parse(argv)
     if pos[:2] == ["zkey", "check"]:   # zkfl/keycheck.py: exit 0 / 1, 2 on unusable arguments
         from . import keycheck
-        return keycheck.cli(pos[2:])
+        return keycheck.cli(pos[2:] + (["--check-ptau"] if "--check-ptau" in argv else []))
+    if pos[:2] == ["powersoftau", "check"]:   # zkfl/ptaucheck.py: the same exit codes
+        from . import ptaucheck
+        return ptaucheck.cli(pos[2:])
+    if pos[:2] == ["powersoftau", "verify"]:
+        print("[ERROR] snarkJS: powersoftau verify is not served: it asserts the contribution transcript, which the "
+              "records written here do not carry; `powersoftau check <pot.ptau>` tests the powers and the Lagrange "
+              "sections", file=sys.stderr)
+        return 99
     try:
         if pos[:2] == ["wtns", "check"] and len(pos) >= 4:
             return wtns_check(pos[2], pos[3])
@@ -160,7 +172,10 @@ def run(argv) -> int:
                   "       snarkjs zkey contribute <in.zkey> <out.zkey> [--name=name] [-e=entropy]\n"
                   "       snarkjs zkey export verificationkey <circuit.zkey> <vkey.json>\n"
                   "       snarkjs wtns check <circuit.r1cs> <witness.wtns>\n"
-                  "       snarkjs zkey check <circuit.r1cs> <pot_final.ptau> <circuit.zkey>", file=sys.stderr)
+                  "       snarkjs zkey check <circuit.r1cs> <pot_final.ptau> <circuit.zkey> [--check-ptau]\n"
+                  "       snarkjs powersoftau check <pot.ptau>\n"
+                  "  (powersoftau verify / ptv are not served: they assert the contribution transcript, which\n"
+                  "   powersoftau check does not read)", file=sys.stderr)
             return 99
     except (ValueError, OSError) as e:
         print(f"[ERROR] snarkJS: {e}", file=sys.stderr)
