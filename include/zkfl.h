@@ -78,7 +78,8 @@ int zkfl_ctx_set_profiling(zkfl_ctx* ctx, int enabled);
  * combined round check's stages; units: proofs),
  * "keycheck_points", "keycheck_rows", "keycheck_msm", "keycheck_pairing" (the key check's stages),
  * "ptaucheck_points", "ptaucheck_scalars", "ptaucheck_msm", "ptaucheck_pairing" (the ptau check's
- * stages, one record per chunk pass; units: points).
+ * stages, one record per chunk pass; units: points),
+ * "secagg_terms", "secagg_fold" (the mask engine's two kernels; units: hashes, output values).
  * Synchronises the device.
  * total_ms: summed event time; units: summed algorithmic units (MSM entries, NTT elements...);
  * median_ms (nullable): median single-launch time, robust to a one-off stalled dispatch. */
@@ -683,6 +684,46 @@ int zkfl_merkle_build(zkfl_ctx* ctx, const uint8_t* leaves, size_t n, uint32_t d
  * root_D = the last 32 B of tree_out. */
 int zkfl_dataset_commit(zkfl_ctx* ctx, const uint8_t* values, size_t n, uint32_t len, uint32_t depth,
                         uint8_t* tree_out);
+
+/* Secure aggregation: pairwise masks derived, signed and summed on the GPU (csrc/secagg.hip).
+ *
+ * The reference's semantics: r_ij[k] = Poseidon(K_ij, round, min(i,j), max(i,j), k) for k < dim
+ * (derivePairwiseMask, tests/full_system_simulation.mjs:181-196; PairwiseMaskDerivation,
+ * src/circuits/secure_masked_update.circom:55-98), sigma_ij = +1 when i < j, else -1 (:100-146 there;
+ * ids compare as unsigned 64-bit integers, the circuit's LessThan(64)), and a client publishes
+ * m_i[k] = g_i[k] + sum_p sigma(i, p) r_ip[k] mod r (:558-637 of the harness).  Its server adds the
+ * masked updates of the clients whose proofs verified (aggregateUpdates, :1137-1199) and decodes a
+ * value above r / 2 as value - r (:1168-1178); the masks cancel only when every client of the group is
+ * in that sum.  Values are 32 B std-form LE and < r, as in the Poseidon block above.
+ *
+ * The mask call: client i has id ids[i], peers peer_ids[t] with keys keys[t] for t in
+ * [peer_ptr[i], peer_ptr[i+1]) (CSR, peer_ptr[0] = 0, so one call serves clients of many groups of
+ * any sizes) and gradient gradients[i]; masked_out[i] = m_i.  A client without peers gets its gradient.
+ *
+ * The aggregate call: group g sums the masked updates masked[m], m in
+ * [member_ptr[g], member_ptr[g+1]) -- the included clients S_g only -- and takes out what the
+ * excluded clients left in them: for every pair t in [pair_ptr[g], pair_ptr[g+1]) of an included
+ * client pair_in[t] and an excluded client pair_out[t] with their key pair_keys[t],
+ *     sum[k] = sum_{i in S} m_i[k] - sum_t sigma(in_t, out_t) r_t[k] mod r   ( = sum_{i in S} g_i[k] ).
+ * Which pairs a group needs, and how their keys come to be revealed, is the caller's protocol
+ * (zkfl/secagg.py::close_groups refuses a group whose pairs are not exactly the needed ones).
+ * signed_out (nullable): the decode above per coordinate; out_of_range[g] (nullable) = 1 when some
+ * coordinate of group g does not fit an int64 -- a mask is still in the sum -- and its signed_out
+ * is then all zero.
+ *
+ * chunk_terms: how many terms (peers / pairs) of a row one GPU lane walks before it writes a
+ * partial sum; 0 = the library's choice.  The bytes are the same for every value.
+ * Errors, all ZKFL_E_ARG before any device work, the message naming the index: a key, gradient,
+ * masked value or round >= r; dim == 0; a *_ptr that does not start at 0 or decreases; a peer equal
+ * to its client's id or repeated in one client's list; pair_in == pair_out; 2^32 or more peers or
+ * pairs in one call.  n == 0 and n_groups == 0 are valid and do nothing. */
+int zkfl_secagg_mask(zkfl_ctx* ctx, size_t n, uint32_t dim, const uint64_t* ids, const uint64_t* peer_ptr,
+                     const uint64_t* peer_ids, const uint8_t* keys, const uint8_t round[32], const uint8_t* gradients,
+                     uint8_t* masked_out, uint32_t chunk_terms);
+int zkfl_secagg_aggregate(zkfl_ctx* ctx, size_t n_groups, uint32_t dim, const uint64_t* member_ptr,
+                          const uint8_t* masked, const uint64_t* pair_ptr, const uint64_t* pair_in,
+                          const uint64_t* pair_out, const uint8_t* pair_keys, const uint8_t round[32],
+                          uint8_t* sum_out, int64_t* signed_out, uint8_t* out_of_range, uint32_t chunk_terms);
 
 /* Dev-ceremony fixed-base multiplications: out[i] = scalars[i] * generator, mont affine. */
 int zkfl_setup_g1_gen_mul(zkfl_ctx* ctx, const uint8_t* scalars, size_t n, uint8_t* out);

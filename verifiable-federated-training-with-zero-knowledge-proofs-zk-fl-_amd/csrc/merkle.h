@@ -24,6 +24,9 @@ void pos_params_raw(uint32_t t, uint8_t* consts_out, uint8_t* xy_out);
 struct PosTables;  // device-resident Montgomery constants for every width (built once per context)
 int pos_tables_create(PosTables** out, hipStream_t st, std::string& err);
 void pos_tables_free(PosTables* p);
+// The tables of one width t in 2..17 (device pointers, Montgomery): C[(8 + rp) * t], M[t][t].
+// For the units that run poseidon_perm0 in kernels of their own (csrc/secagg.hip).
+void pos_tables_width(const PosTables* p, uint32_t t, const Fr** C, const Fr** M, uint32_t* rp);
 
 // out[i] = in[i] in Montgomery form (device, n elements)
 hipError_t fr_to_mont_batch(const Fr* in, size_t n, Fr* out, hipStream_t st);

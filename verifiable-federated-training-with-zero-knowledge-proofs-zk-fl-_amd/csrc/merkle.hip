@@ -304,6 +304,12 @@ void pos_tables_free(PosTables* p) {
   delete p;
 }
 
+void pos_tables_width(const PosTables* p, uint32_t t, const Fr** C, const Fr** M, uint32_t* rp) {
+  *C = p->w[t].C;
+  *M = p->w[t].M;
+  *rp = p->w[t].rp;
+}
+
 int pos_tables_create(PosTables** out, hipStream_t st, std::string& err) {
   // host: raw constants of every width; device: Montgomery form, MDS inverses, zero hashes
   size_t total = 0, off[18] = {}, nc[18] = {};

@@ -233,6 +233,8 @@ struct zkfl_vkey {
 namespace zkfl {
 void ctx_retain(zkfl_ctx* ctx);
 void ctx_release(zkfl_ctx* ctx);  // drops one reference; the last one tears the context down
+// csrc/zkfl.hip: the context's Poseidon tables (ctx->pos), built by the first hashing call
+int pos_ready(zkfl_ctx* ctx);
 // csrc/prove.hip: the key's idx-th slot (idx % max_slots), made on first use; all of its slots and
 // its witness pipe released (key_release, csrc/key_load.hip)
 int get_slot(zkfl_key* k, size_t idx, ProofSlot** out);

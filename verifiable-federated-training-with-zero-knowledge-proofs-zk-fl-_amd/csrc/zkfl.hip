@@ -105,13 +105,6 @@ int run_msm_primitive(zkfl_ctx* ctx, const uint8_t* bases, const uint8_t* scalar
   return ZKFL_OK;
 }
 
-int pos_ready(zkfl_ctx* ctx) {
-  if (ctx->pos) return ZKFL_OK;
-  std::string err;
-  int rc = pos_tables_create(&ctx->pos, ctx->st, err);
-  return rc ? fail(rc, err) : ZKFL_OK;
-}
-
 int check_fr_array(const uint8_t* v, size_t count, const char* what) {
   for (size_t i = 0; i < count; i++) {
     uint32_t w[8];
@@ -145,6 +138,13 @@ int tree_args(zkfl_ctx* ctx, size_t n, uint32_t depth, const void* in, const voi
 }
 
 }  // namespace
+
+int zkfl::pos_ready(zkfl_ctx* ctx) {
+  if (ctx->pos) return ZKFL_OK;
+  std::string err;
+  int rc = pos_tables_create(&ctx->pos, ctx->st, err);
+  return rc ? fail(rc, err) : ZKFL_OK;
+}
 
 void zkfl::ctx_retain(zkfl_ctx* ctx) { ctx->refs.fetch_add(1, std::memory_order_relaxed); }
 

@@ -36,6 +36,16 @@
         --combined: answer the round by one random combination with one final exponentiation
         (verify_round; the per-proof path gives the verdicts when it fails).  Same lines and exit
         codes; the report goes to stderr
+    python -m zkfl aggregate-round <round.json>              aggregateUpdates (:1137-1199) with the masks of the
+        excluded clients taken out.  round.json: {"round", "dim", "groups": [{"clients": [{"id",
+        "accepted", "public"}], "revealed": [{"in", "out", "key"}]}]}; "public" is an accepted client's
+        secure_masked_update public.json (client_id, round, ..., masked_update at signals 7..7+dim,
+        :999-1000; relative paths are taken from the manifest's directory), "revealed" the pairwise key
+        of every (accepted, excluded) pair of the group.  Prints one JSON line per group, {"group",
+        "clients", "sum": [signed integers], "mean"}; exit 0, 1 if a group's sum is out of range (a mask
+        is still in it), 2 on a manifest of another shape, a missing file, a public.json whose client_id
+        or round disagrees with the manifest, a missing key or a key that is not needed (all decided
+        before the GPU is touched)
 
 <circuit> is one of zkfl.circuits.CIRCUITS (poseidon_hash2, sgd_verified, sgd_step_v5,
 balance_unified, secure_masked_update) followed by its integer template parameters.  GPU
@@ -227,6 +237,88 @@ def cmd_verify_round(args):
     return 0 if all(oks) else 1
 
 
+def _aggregate_manifest(path):
+    """round.json of `aggregate-round` -> (round, dim, groups for secagg.close_groups), or None with a
+    message on stderr.  Everything that can be wrong with the manifest is decided here, on the host."""
+    from . import secagg
+
+    def bad(msg):
+        print(f"[ERROR] zkfl: {path}: {msg}", file=sys.stderr)
+
+    try:
+        with open(path) as f:
+            man = json.load(f)
+    except (OSError, ValueError) as e:
+        return bad(e)
+    shape = ('expected {"round", "dim", "groups": [{"clients": [{"id", "accepted", "public"}], '
+             '"revealed": [{"in", "out", "key"}]}]}')
+    try:
+        rnd, dim = int(man["round"]), int(man["dim"])
+        if dim < 1 or not 0 <= rnd < zkey.R or not isinstance(man["groups"], list):
+            return bad(shape)
+        parsed = []
+        for grp in man["groups"]:
+            clients = [(int(c["id"]), bool(c["accepted"]), c.get("public")) for c in grp["clients"]]
+            revealed = [(int(t["in"]), int(t["out"]), int(t["key"])) for t in grp["revealed"]]
+            if any(acc and not isinstance(pub, str) for _, acc, pub in clients):
+                return bad(shape)
+            if not all(0 <= t[2] < zkey.R for t in revealed):
+                return bad("a revealed key is not a field element")
+            if not all(0 <= i < 1 << 64 for i in [c[0] for c in clients] + [x for t in revealed for x in t[:2]]):
+                return bad("a client id is not an unsigned 64-bit integer")
+            parsed.append((clients, revealed))
+    except (KeyError, TypeError, ValueError, AttributeError):
+        return bad(shape)
+    base = os.path.dirname(os.path.abspath(path))
+    groups = []
+    for g, (clients, revealed) in enumerate(parsed):
+        accepted = {}
+        for cid, acc, pub in clients:
+            if not acc:
+                continue
+            pub = os.path.join(base, pub)
+            if not os.path.isfile(pub):
+                return bad(f"no such file: {pub}")
+            try:
+                sig = [int(x) for x in json.load(open(pub))]
+            except (OSError, ValueError, TypeError) as e:
+                return bad(f"{pub}: {e}")
+            # secure_masked_update's public signals: client_id, round, root_D, root_G, root_W, root_K,
+            # tauSquared, masked_update[dim] (tests/full_system_simulation.mjs:999-1000)
+            if len(sig) != 7 + dim:
+                return bad(f"{pub}: expected {7 + dim} public signals, found {len(sig)}")
+            if sig[0] != cid or sig[1] != rnd:
+                return bad(f"{pub}: client_id {sig[0]}, round {sig[1]} where the manifest says client {cid}, round {rnd}")
+            if cid in accepted:
+                return bad(f"group {g}: client {cid} is listed twice")
+            if not all(0 <= x < zkey.R for x in sig[7:7 + dim]):
+                return bad(f"{pub}: a masked_update value is not a field element")
+            accepted[cid] = sig[7:7 + dim]
+        try:
+            secagg.check_group(g, [c[0] for c in clients], list(accepted), revealed)
+        except ValueError as e:
+            return bad(e)
+        groups.append({"roster": [c[0] for c in clients], "accepted": accepted, "revealed": revealed})
+    return rnd, dim, groups
+
+
+def cmd_aggregate_round(args):
+    man = _aggregate_manifest(args.round)
+    if man is None:
+        return 2
+    from . import secagg
+    rnd, _, groups = man
+    with _ctx() as ctx:
+        sums = secagg.close_groups(ctx, groups, rnd)
+    for g, s in enumerate(sums):
+        line = {"group": g, "clients": s["clients"], "sum": s["sum"],
+                "mean": None if s["sum"] is None else [x / s["clients"] for x in s["sum"]]}
+        if s["out_of_range"]:
+            line["out_of_range"] = True
+        print(json.dumps(line))
+    return 1 if any(s["out_of_range"] for s in sums) else 0
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     if snarkjs_cli.routes(argv):   # snarkjs ceremony strings and `wtns check` (zkfl/snarkjs_cli.py)
@@ -273,10 +365,13 @@ def main(argv=None):
     sp.add_argument("round")
     sp.add_argument("--combined", action="store_true",
                     help="one random combination and one final exponentiation for the whole round")
+    sp = sub.add_parser("aggregate-round")
+    sp.add_argument("round")
     args = ap.parse_args(argv)
     fn = {"compile": cmd_compile, "info": cmd_info, "setup": cmd_setup,
           "r1cs-info": cmd_r1cs_info, "setup-r1cs": cmd_setup_r1cs, "export-vk": cmd_export_vk,
-          "wtns": cmd_wtns, "prove": cmd_prove, "verify": cmd_verify, "verify-round": cmd_verify_round}[args.cmd]
+          "wtns": cmd_wtns, "prove": cmd_prove, "verify": cmd_verify, "verify-round": cmd_verify_round,
+          "aggregate-round": cmd_aggregate_round}[args.cmd]
     try:
         return fn(args) or 0
     except native.ZkflError as e:

@@ -215,6 +215,10 @@ SIGNATURES = {
                                   C.POINTER(ZkeyReport)]),
     "zkfl_ptau_parse": (C.c_int, [_P, C.c_size_t, C.POINTER(PtauHeader)]),
     "zkfl_ptau_check": (C.c_int, [_P, _P, C.c_size_t, C.c_char_p, C.c_uint32, C.POINTER(PtauReportC)]),
+    # buffers as addresses: the callers hand numpy arrays over (Context.secagg_mask / secagg_aggregate)
+    "zkfl_secagg_mask": (C.c_int, [_P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.c_uint32]),
+    "zkfl_secagg_aggregate": (C.c_int, [_P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        C.c_uint32]),
 }
 
 
@@ -308,6 +312,28 @@ def device_count() -> int:
 
 def _buf(n):
     return (C.c_uint8 * n)()
+
+
+def _u64(a):
+    """Unsigned 64-bit integers as a contiguous numpy array."""
+    import numpy as np
+    return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+
+
+def _u8(b):
+    """bytes, or an array of uint8, as a flat contiguous uint8 array (no copy where it is one)."""
+    import numpy as np
+    if isinstance(b, (bytes, bytearray, memoryview)):
+        return np.frombuffer(b, dtype=np.uint8)
+    b = np.ascontiguousarray(b)
+    if b.dtype != np.uint8:
+        raise ZkflError(-1, f"expected bytes or a uint8 array, got {b.dtype}")
+    return b.reshape(-1)
+
+
+def _addr(a):
+    """A numpy array's address for a void* parameter (None for an empty one)."""
+    return a.ctypes.data if a is not None and a.size else None
 
 
 def _proofs(out, n) -> list:
@@ -633,6 +659,70 @@ class Context(_Handle):
         out = _buf(32 * ((2 << depth) - 1))
         check(lib().zkfl_dataset_commit(self.h, values, n, ln, depth, out))
         return bytes(out)
+
+    def poseidon_batch_raw(self, arity: int, rows):
+        """Byte form of poseidon_batch: rows = n x arity x 32 B std (bytes or a uint8 array) -> a uint8
+        array (n, 32).  For batches too large to go through Python integers."""
+        import numpy as np
+        rows = _u8(rows)
+        n = rows.size // (32 * arity)
+        assert rows.size == 32 * arity * n
+        out = np.zeros((n, 32), np.uint8)
+        if n:
+            check(lib().zkfl_poseidon_batch(self.h, arity, n, C.cast(rows.ctypes.data, C.c_char_p),
+                                            C.cast(out.ctypes.data, _U8P)))
+        return out
+
+    # secure aggregation (csrc/secagg.hip; zkfl/secagg.py holds the list-level interface)
+    def secagg_mask(self, ids, peer_ptr, peer_ids, keys, rnd: int, gradients, dim: int, chunk_terms: int = 0):
+        """zkfl_secagg_mask: ids (n), peer_ptr (n + 1, CSR) and peer_ids (T) as unsigned 64-bit
+        integers; keys (T x 32 B) and gradients (n x dim x 32 B) std-form field elements as bytes or
+        uint8 arrays; rnd an integer < r.  -> the masked updates, a uint8 array (n, dim, 32)."""
+        import numpy as np
+        ids, peer_ptr, peer_ids = _u64(ids), _u64(peer_ptr), _u64(peer_ids)
+        keys, gradients = _u8(keys), _u8(gradients)
+        n = ids.size
+        if peer_ptr.size != n + 1:
+            raise ZkflError(-1, f"secagg_mask: peer_ptr holds {peer_ptr.size} entries for {n} clients")
+        t = int(peer_ptr[n])
+        if t < 1 << 32 and (peer_ids.size != t or keys.size != 32 * t):
+            raise ZkflError(-1, f"secagg_mask: peer_ptr counts {t} peers, peer_ids holds {peer_ids.size} "
+                                f"and keys {keys.size // 32}")
+        if gradients.size != 32 * n * dim:
+            raise ZkflError(-1, f"secagg_mask: expected {n} x {dim} gradient values (32 B each)")
+        out = np.zeros((n, dim, 32), np.uint8)
+        check(lib().zkfl_secagg_mask(self.h, n, dim, _addr(ids), _addr(peer_ptr), _addr(peer_ids), _addr(keys),
+                                     int(rnd).to_bytes(32, "little"), _addr(gradients), _addr(out), chunk_terms))
+        return out
+
+    def secagg_aggregate(self, member_ptr, masked, pair_ptr, pair_in, pair_out, pair_keys, rnd: int, dim: int,
+                         chunk_terms: int = 0, decode: bool = True):
+        """zkfl_secagg_aggregate: member_ptr / pair_ptr (n_groups + 1, CSR), pair_in / pair_out (P)
+        as unsigned 64-bit integers; masked (M x dim x 32 B, the included members' updates, group after
+        group) and pair_keys (P x 32 B) as bytes or uint8 arrays.  -> (sums: uint8 (n_groups, dim, 32),
+        signed: int64 (n_groups, dim), out_of_range: bool (n_groups)); the last two None when not
+        decode."""
+        import numpy as np
+        member_ptr, pair_ptr, pair_in, pair_out = _u64(member_ptr), _u64(pair_ptr), _u64(pair_in), _u64(pair_out)
+        masked, pair_keys = _u8(masked), _u8(pair_keys)
+        g = member_ptr.size - 1
+        if g < 0 or pair_ptr.size != g + 1:
+            raise ZkflError(-1, "secagg_aggregate: member_ptr and pair_ptr must hold n_groups + 1 entries each")
+        m, p = int(member_ptr[g]), int(pair_ptr[g])
+        if p < 1 << 32 and (pair_in.size != p or pair_out.size != p or pair_keys.size != 32 * p):
+            raise ZkflError(-1, f"secagg_aggregate: pair_ptr counts {p} pairs, the pair arrays hold "
+                                f"{pair_in.size}, {pair_out.size} and {pair_keys.size // 32}")
+        if m < 1 << 32 and masked.size != 32 * m * dim:
+            raise ZkflError(-1, f"secagg_aggregate: expected {m} x {dim} masked values (32 B each)")
+        sums = np.zeros((g, dim, 32), np.uint8)
+        signed = np.zeros((g, dim), np.int64) if decode else None
+        oor = np.zeros(g, np.uint8) if decode else None
+        check(lib().zkfl_secagg_aggregate(self.h, g, dim, _addr(member_ptr), _addr(masked), _addr(pair_ptr),
+                                          _addr(pair_in), _addr(pair_out), _addr(pair_keys),
+                                          int(rnd).to_bytes(32, "little"), _addr(sums),
+                                          _addr(signed) if decode else None, _addr(oor) if decode else None,
+                                          chunk_terms))
+        return sums, signed, (oor.astype(bool) if decode else None)
 
     # multi-key batches (one federated round: several circuits' proofs interleaved on one device)
     def prove_multi(self, jobs, rs: bytes | None = None) -> list:
