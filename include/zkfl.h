@@ -285,6 +285,25 @@ int zkfl_debug_glv_split(const uint8_t k[32], uint8_t out[40]);
  * groth16_prove). */
 int zkfl_debug_g1_glv_mul(zkfl_ctx* ctx, size_t n, const uint8_t* points, const uint8_t* scalars, uint8_t* out);
 
+/* The MSM stage of a small key's proof on a caller's sets (parity hook; a test entry: its inputs need
+ * not come from a key): n1 (1..4) G1 sets sorted in the same four launches and accumulated in one
+ * launch, a G2 set accumulated from set b's sorted pairs with set b's entry count, then the tails --
+ * the very function a small key's proofs run (csrc/prove.hip front_msm).  Set i has n[i] bases (mont
+ * affine, 64 B, (0, 0) = infinity, as zkfl_msm_g1 takes them) and n_scalars[i] scalars (32 B std, < r).
+ * sidx == NULL or sidx[i] == NULL: base j takes scalar j (n_scalars[i] >= n[i]).  Otherwise sidx[i]
+ * holds n[i] u32, a key's index map: an entry below extra_start[i] addresses scalars[i], any other
+ * entry - extra_start[i] addresses extra[i] (n_extra[i] scalars).  bases_g2: n_b = n[b] G2 bases
+ * (mont affine, 128 B), base j riding on set b's base j.  fast: the shorter-chain bucket reduction.
+ * joint = 1: the G1 and G2 tails as one batch, as proofs run them; 0: the batched G1 tails, then the
+ * G2 tail.  Window width: msm_pick_c of the largest set (ZKFL_MSM_C forces one).  out_g1: n1 x 64 B,
+ * out_g2: 128 B, std affine, infinity = zeros.  Sets of more than 2^17 entries, a scalar >= r (the
+ * error names its index), an index outside its vector, a null argument or a bad count return
+ * ZKFL_E_ARG before any device call. */
+int zkfl_debug_msm_front(zkfl_ctx* ctx, uint32_t n1, const size_t* n, const uint8_t* const* bases,
+                         const uint8_t* const* scalars, const size_t* n_scalars, const uint32_t* const* sidx,
+                         const uint32_t* extra_start, const uint8_t* const* extra, const size_t* n_extra, uint32_t b,
+                         const uint8_t* bases_g2, size_t n_b, int fast, int joint, uint8_t* out_g1, uint8_t out_g2[128]);
+
 /* Wave-level kernel timeline (measurement only; libraries built with -DZK_WTRACE=1, otherwise every
  * op returns ZKFL_E_ARG).  op 1: start recording into a fresh device buffer of `cap` records (any
  * earlier one is freed); op 2: wait for the device, stop recording, copy min(count, cap) records of

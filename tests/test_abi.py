@@ -36,6 +36,9 @@ def test_version_and_error_paths_without_device():
     buf = (ctypes.c_uint8 * 64)()
     assert L.zkfl_ntt_coset(None, buf, 1) == -1
     assert L.zkfl_debug_ntt_coset(None, buf, 1, 1, 2, -1) == -1
+    one, ptr = (ctypes.c_size_t * 1)(1), (ctypes.c_char_p * 1)(bytes(buf))
+    assert L.zkfl_debug_msm_front(None, 1, one, ptr, ptr, one, None, None, None, None, 0, bytes(128), 1, 1, 1,
+                                  buf, (ctypes.c_uint8 * 128)()) == -1
 
 
 def test_glv_split_host():

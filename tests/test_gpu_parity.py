@@ -147,7 +147,10 @@ def test_msm_g1_matches_oracle_pippenger(gpu_ctx):
 
 
 # every case at both window widths a key can take (csrc/msm_api.h msm_pick_c: 14 bits for small
-# keys, 16 for large ones; ZKFL_MSM_C forces one)
+# keys, 16 for large ones; ZKFL_MSM_C forces one).  These cases run the single-MSM path (msm_run
+# with one job: the single-job sort without an index map, k_msm_accumulate, the one-curve tails, the
+# throughput reduction); tests/test_gpu_msm_front.py runs them through the small keys' front path
+# (multi-job sort and accumulation, index maps, B2 from B1's sort, joint tails, both reductions)
 @pytest.mark.parametrize("width", [14, 16])
 @pytest.mark.parametrize("case", ["zeros", "ones", "small", "neg", "dup", "cancel", "inf_base", "max", "binedge",
                                   "binedge17", "binedge14"])

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "assemble.h"
+#include "devbufs.h"
 #include "glv.h"
 #include "groups.h"
 #include "host_parse.h"
@@ -280,6 +281,16 @@ int get_rs(const uint8_t* rs, uint32_t out[16]) {
   return ZKFL_OK;
 }
 
+// count scalars of 32 B, each < r; the error names the first that is not
+int check_fr(const uint8_t* v, size_t count, const std::string& what) {
+  for (size_t i = 0; i < count; i++) {
+    uint32_t w[8];
+    memcpy(w, v + 32 * i, 32);
+    if (!fr_lt_r(w)) return fail(ZKFL_E_ARG, what + " " + std::to_string(i) + " is not < r");
+  }
+  return ZKFL_OK;
+}
+
 // What a proof is run for.
 enum class ProofMode {
   Proof,      // a whole proof: its 256 bytes assembled into the slot's pinned buffer
@@ -438,13 +449,13 @@ hipError_t abc_ntt(zkfl_key* k, ProofSlot* s, const Fr* d_w, hipStream_t st, con
 }
 
 // Step: B2 from B1's sort.  `sorted` holds the pairs of B's digit sort (whoever sorted, on
-// whichever stream, ordered before st here); B2 accumulates from them on st before anything reuses
-// that scratch.  Its tail counts with B1's nnz, copied unless the two alias (ProofSlot::nnz_alias).
-hipError_t b2_from_b1_sort(const MsmBases<Fq2Ops>& bB2, ProofSlot* s, const MsmScratch<FqOps>& sorted, hipStream_t st,
-                           Profiler* prof) {
-  if (!s->nnz_alias)
-    ZK_CHECK(hipMemcpyAsync(s->g2t.nnz, s->g1t[1].nnz, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-  return msm_accumulate_sorted(bB2, sorted.keys_out, sorted.vals_out, s->g2t, st, prof, "msm_accumulate_g2");
+// whichever stream, ordered before st here); B2 accumulates from them into its tail g2t on st before
+// anything reuses that scratch.  Its tail counts with B1's nnz (b1_nnz), copied unless the two alias
+// (ProofSlot::nnz_alias).
+hipError_t b2_from_b1_sort(const MsmBases<Fq2Ops>& bB2, MsmTail<Fq2Ops>& g2t, const uint32_t* b1_nnz, bool nnz_alias,
+                           const MsmScratch<FqOps>& sorted, hipStream_t st, Profiler* prof) {
+  if (!nnz_alias) ZK_CHECK(hipMemcpyAsync(g2t.nnz, b1_nnz, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  return msm_accumulate_sorted(bB2, sorted.keys_out, sorted.vals_out, g2t, st, prof, "msm_accumulate_g2");
 }
 
 // Step: what leaves a one-stream schedule -- a split proof's part and its download, a proof's
@@ -497,7 +508,7 @@ int run_lowlat(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Pro
   HIP_TRY(msm_sort(b.B1, s->g1s_b, s->g1t[1].nnz, W, E, sb), "msm B sort");
   HIP_TRY(hipEventRecord(ev, sb), "event");
   HIP_TRY(hipStreamWaitEvent(sa, ev, 0), "wait");
-  HIP_TRY(b2_from_b1_sort(b.B2, s, s->g1s_b, sb, prof), "msm B2");
+  HIP_TRY(b2_from_b1_sort(b.B2, s->g2t, s->g1t[1].nnz, s->nnz_alias, s->g1s_b, sb, prof), "msm B2");
   HIP_TRY(msm_tails(&t2, &o2, 1, sb, p.fast_wsum), "msm B2 tail");
   HIP_TRY(hipEventRecord(ev_b2, sb), "event");
   // lat1: B1 (B's pairs), A, their tails, then T = s pi_A + r B1 and pi_a
@@ -521,6 +532,50 @@ int run_lowlat(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Pro
   return ZKFL_OK;
 }
 
+// The MSM stage of a small key's proof (run_front) over n1 G1 sets and the G2 set that rides on
+// set ib's sort: the n1 sorts in the same four launches (each in its own scratch), the n1
+// accumulations in one launch, B2 from set ib's pairs, then the tails -- joint: G1 and G2 as one
+// batch (msm_tails_joint, what proofs run); otherwise the batched G1 tails and the G2 tail after
+// them (msm_tails, the form of run_chain and run_lowlat).  Every tail must have been emptied.  The
+// parity hook zkfl_debug_msm_front runs this same function on a caller's sets.
+struct FrontMsm {
+  int n1 = 0;                                    // G1 sets (a proof: A, B1, C + H)
+  const MsmBases<FqOps>* bases[MSM_TAIL_MAX] = {};
+  MsmScratch<FqOps>* scratch[MSM_TAIL_MAX] = {};
+  MsmTail<FqOps>* tails[MSM_TAIL_MAX] = {};
+  const uint32_t* scalars[MSM_TAIL_MAX] = {};    // per set: its scalar vector
+  const uint32_t* extra[MSM_TAIL_MAX] = {};      // and what its index map's extra slots address
+  G1P* outs[MSM_TAIL_MAX] = {};
+  int ib = 1;                                    // the set that plays B1
+  const MsmBases<Fq2Ops>* b2 = nullptr;
+  MsmTail<Fq2Ops>* t2 = nullptr;
+  bool nnz_alias = false;                        // t2->nnz is tails[ib]->nnz (no copy)
+  G2P* out2 = nullptr;
+};
+int front_msm(const FrontMsm& m, hipStream_t st, bool fast, bool joint, Profiler* prof) {
+  const int n = m.n1;
+  uint32_t* nn[MSM_TAIL_MAX] = {};
+  const uint16_t* kk[MSM_TAIL_MAX] = {};
+  const uint32_t* vv[MSM_TAIL_MAX] = {};
+  for (int i = 0; i < n; i++) nn[i] = m.tails[i]->nnz;
+  HIP_TRY(msm_sort_multi(m.bases, m.scratch, nn, m.scalars, m.extra, n, st), "msm A, B1, C+H sorts");
+  for (int i = 0; i < n; i++) {
+    kk[i] = m.scratch[i]->keys_out;
+    vv[i] = m.scratch[i]->vals_out;
+  }
+  HIP_TRY(msm_accumulate_sorted_multi(m.bases, kk, vv, m.tails, n, st), "msm A, B1, C+H");
+  HIP_TRY(b2_from_b1_sort(*m.b2, *m.t2, m.tails[m.ib]->nnz, m.nnz_alias, *m.scratch[m.ib], st, prof), "msm B2");
+  MsmTail<Fq2Ops>* t2 = m.t2;
+  G2P* o2 = m.out2;
+  if (joint) {
+    HIP_TRY(msm_tails_joint(m.tails, m.outs, n, &t2, &o2, 1, st, fast), "msm tails (G1 + G2)");
+  } else {
+    HIP_TRY(msm_tails(m.tails, m.outs, n, st, fast), "msm tails");
+    HIP_TRY(msm_tails(&t2, &o2, 1, st, fast), "msm B2 tail");
+  }
+  return ZKFL_OK;
+}
+
 // Small keys, one stream:
 //   [start] ABC, coset NTT, join, A, B1 and C + H sorted together (each in its own scratch) and
 //   accumulated in one launch, B2 from B1's pairs, the G1 and G2 tails as one batch, [finish]
@@ -531,21 +586,26 @@ int run_front(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Prof
   const uint32_t *W = (const uint32_t*)d_w, *E = (const uint32_t*)s->extra;
   HIP_TRY(abc_ntt(k, s, d_w, st, p, prof), "ntt");
   const PlanBases b = plan_bases(k, p);
+  FrontMsm m;
+  m.n1 = 3;
   const MsmBases<FqOps>* bs[3] = {&b.A, &b.B1, &b.CH};
   MsmScratch<FqOps>* ss[3] = {&s->g1s_a, &s->g1s_b, &s->g1s};
-  MsmTail<FqOps>* tails[3] = {&s->g1t[0], &s->g1t[1], &s->g1t[2]};
-  uint32_t* nn[3] = {s->g1t[0].nnz, s->g1t[1].nnz, s->g1t[2].nnz};
-  const uint32_t* sc[3] = {W, W, W};
   const uint32_t* ex[3] = {E, E, (const uint32_t*)s->h};
-  HIP_TRY(msm_sort_multi(bs, ss, nn, sc, ex, 3, st), "msm A, B1, C+H sorts");
-  const uint16_t* kk[3] = {ss[0]->keys_out, ss[1]->keys_out, ss[2]->keys_out};
-  const uint32_t* vv[3] = {ss[0]->vals_out, ss[1]->vals_out, ss[2]->vals_out};
-  HIP_TRY(msm_accumulate_sorted_multi(bs, kk, vv, tails, 3, st), "msm A, B1, C+H");
-  HIP_TRY(b2_from_b1_sort(b.B2, s, s->g1s_b, st, prof), "msm B2");
-  G1P* outs[3] = {s->res + 0, s->res + 1, s->res + 2};
-  MsmTail<Fq2Ops>* t2 = &s->g2t;
-  G2P* o2 = s->resB2;
-  HIP_TRY(msm_tails_joint(tails, outs, 3, &t2, &o2, 1, st, p.fast_wsum), "msm tails (G1 + G2)");
+  for (int i = 0; i < 3; i++) {
+    m.bases[i] = bs[i];
+    m.scratch[i] = ss[i];
+    m.tails[i] = &s->g1t[i];
+    m.scalars[i] = W;
+    m.extra[i] = ex[i];
+    m.outs[i] = s->res + i;
+  }
+  m.ib = 1;
+  m.b2 = &b.B2;
+  m.t2 = &s->g2t;
+  m.nnz_alias = s->nnz_alias;
+  m.out2 = s->resB2;
+  const int rc = front_msm(m, st, p.fast_wsum, true, prof);
+  if (rc) return rc;
   return finish(k, s, p, prof);
 }
 
@@ -579,7 +639,7 @@ int run_chain(zkfl_key* k, ProofSlot* s, const Fr* d_w, const ProofPlan& p, Prof
     HIP_TRY(msm_sort(b.B1, sB, s->g1t[1].nnz, W, E, st), "msm B1 sort");
     HIP_TRY(msm_accumulate_sorted(b.B1, sB.keys_out, sB.vals_out, s->g1t[1], st, prof, "msm_accumulate_g1"),
             "msm B1");
-    HIP_TRY(b2_from_b1_sort(b.B2, s, sB, st, prof), "msm B2");
+    HIP_TRY(b2_from_b1_sort(b.B2, s->g2t, s->g1t[1].nnz, s->nnz_alias, sB, st, prof), "msm B2");
     if (!p.joint_tails) HIP_TRY(msm_tails(&t2, &o2, 1, st, p.fast_wsum), "msm B2 tail");
   } else {
     HIP_TRY(msm_accumulate(b.B1, sB, s->g1t[1], W, E, st, prof, "msm_accumulate_g1"), "msm B1");
@@ -1328,6 +1388,112 @@ int zkfl_debug_abc(zkfl_ctx* ctx, zkfl_key* key, const zkfl_witness* w, int grou
   if (e != hipSuccess) return hip_fail(e, "debug abc");
   memcpy(counts_out, s->pinned + MISS_OFF, 12);
   if (!p.group_rows) counts_out[1] = counts_out[2] = 0;
+  return ZKFL_OK;
+}
+
+int zkfl_debug_msm_front(zkfl_ctx* ctx, uint32_t n1, const size_t* n, const uint8_t* const* bases,
+                         const uint8_t* const* scalars, const size_t* n_scalars, const uint32_t* const* sidx,
+                         const uint32_t* extra_start, const uint8_t* const* extra, const size_t* n_extra, uint32_t b,
+                         const uint8_t* bases_g2, size_t n_b, int fast, int joint, uint8_t* out_g1, uint8_t out_g2[128]) {
+  constexpr size_t CAP = (size_t)1 << 17;
+  if (!ctx || !n || !bases || !scalars || !n_scalars || !out_g1 || !out_g2)
+    return fail(ZKFL_E_ARG, "msm front: null argument");
+  if (n1 < 1 || n1 > (uint32_t)MSM_TAIL_MAX || b >= n1 || (fast != 0 && fast != 1) || (joint != 0 && joint != 1))
+    return fail(ZKFL_E_ARG, "msm front: 1..4 G1 sets, b one of them, fast and joint 0 or 1");
+  // B2 accumulates from set b's sorted pairs, which index set b's bases: one G2 base per G1 base
+  if (n_b != n[b] || (n_b && !bases_g2)) return fail(ZKFL_E_ARG, "msm front: the G2 set needs one base per base of set b");
+  size_t most = 0;
+  for (uint32_t i = 0; i < n1; i++) {
+    const std::string set = "msm front: set " + std::to_string(i);
+    const bool mapped = sidx && sidx[i];
+    const size_t ne = mapped && n_extra ? n_extra[i] : 0;
+    if (n[i] > CAP || n_scalars[i] > CAP || ne > CAP) return fail(ZKFL_E_ARG, set + ": more than 2^17 entries");
+    if ((n[i] && !bases[i]) || (n_scalars[i] && !scalars[i])) return fail(ZKFL_E_ARG, set + ": null argument");
+    if (mapped && (!extra_start || (ne && (!extra || !extra[i])))) return fail(ZKFL_E_ARG, set + ": null argument");
+    if (int rc = check_fr(scalars[i], n_scalars[i], set + ": scalar")) return rc;
+    if (ne)
+      if (int rc = check_fr(extra[i], ne, set + ": extra scalar")) return rc;
+    // every scalar a base reads lies inside one of the two vectors (msm_sort.hip msm_for_digits)
+    if (!mapped && n_scalars[i] < n[i]) return fail(ZKFL_E_ARG, set + ": fewer scalars than bases");
+    for (size_t j = 0; mapped && j < n[i]; j++) {
+      const uint32_t si = sidx[i][j];
+      if (si < extra_start[i] ? si >= n_scalars[i] : (size_t)(si - extra_start[i]) >= ne)
+        return fail(ZKFL_E_ARG, set + ": sidx " + std::to_string(j) + " is out of range");
+    }
+    most = std::max(most, n[i]);
+  }
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = ctx->st;
+  struct Engine {  // released on every exit path
+    MsmBases<FqOps> mb[MSM_TAIL_MAX];
+    MsmScratch<FqOps> ms[MSM_TAIL_MAX];
+    MsmTail<FqOps> mt[MSM_TAIL_MAX];
+    MsmBases<Fq2Ops> mb2;
+    MsmTail<Fq2Ops> mt2;
+    ~Engine() {
+      for (auto& x : mb) msm_bases_free(x);
+      for (auto& x : ms) msm_scratch_free(x);
+      for (auto& x : mt) msm_tail_free(x);
+      msm_bases_free(mb2);
+      msm_tail_free(mt2);
+    }
+  } E;
+  DevBufs D;
+  const char* const where = "msm front";
+  const int c = msm_pick_c(most);  // as key load: one width for every set of the key
+  FrontMsm m;
+  m.n1 = (int)n1;
+  G1P* d_r;
+  G2P* d_r2;
+  uint32_t* d_o;
+  HIP_TRY(D.get(&d_r, n1), where);
+  HIP_TRY(D.get(&d_r2, 1), where);
+  HIP_TRY(D.get(&d_o, n1 * 16 + 32), where);
+  for (uint32_t i = 0; i < n1; i++) {
+    const bool mapped = sidx && sidx[i];
+    const size_t ne = mapped && n_extra ? n_extra[i] : 0;
+    G1Aff* d_b;
+    uint32_t *d_s, *d_e;
+    // scratch and tail by the set's own base count, as a slot's are
+    HIP_TRY(msm_bases_alloc(E.mb[i], n[i], c), where);
+    HIP_TRY(msm_scratch_alloc(E.ms[i], n[i], c, st), where);
+    HIP_TRY(msm_tail_alloc(E.mt[i], n[i], c), where);
+    HIP_TRY(D.get(&d_b, n[i]), where);
+    HIP_TRY(D.get(&d_s, n_scalars[i] * 8), where);
+    HIP_TRY(D.get(&d_e, ne * 8), where);
+    if (n[i]) HIP_TRY(hipMemcpyAsync(d_b, bases[i], n[i] * sizeof(G1Aff), hipMemcpyHostToDevice, st), where);
+    if (n_scalars[i]) HIP_TRY(hipMemcpyAsync(d_s, scalars[i], n_scalars[i] * 32, hipMemcpyHostToDevice, st), where);
+    if (ne) HIP_TRY(hipMemcpyAsync(d_e, extra[i], ne * 32, hipMemcpyHostToDevice, st), where);
+    HIP_TRY(msm_bases_set(E.mb[i], d_b, mapped ? sidx[i] : nullptr, mapped ? extra_start[i] : 0xFFFFFFFFu, st), where);
+    m.bases[i] = &E.mb[i];
+    m.scratch[i] = &E.ms[i];
+    m.tails[i] = &E.mt[i];
+    m.scalars[i] = d_s;
+    m.extra[i] = d_e;
+    m.outs[i] = d_r + i;
+  }
+  G2Aff* d_b2;
+  HIP_TRY(msm_bases_alloc(E.mb2, n_b, c), where);
+  HIP_TRY(msm_tail_alloc(E.mt2, n_b, c), where);  // its own nnz: the copy of b2_from_b1_sort runs
+  HIP_TRY(D.get(&d_b2, n_b), where);
+  if (n_b) HIP_TRY(hipMemcpyAsync(d_b2, bases_g2, n_b * sizeof(G2Aff), hipMemcpyHostToDevice, st), where);
+  HIP_TRY(msm_bases_set(E.mb2, d_b2, nullptr, 0xFFFFFFFFu, st), where);
+  m.ib = (int)b;
+  m.b2 = &E.mb2;
+  m.t2 = &E.mt2;
+  m.nnz_alias = false;
+  m.out2 = d_r2;
+  // what k_proof_start does for a proof: every tail emptied
+  MsmTail<Fq2Ops>* t2 = &E.mt2;
+  HIP_TRY(msm_tails_reset(m.tails, m.n1, st), where);
+  HIP_TRY(msm_tails_reset(&t2, 1, st), where);
+  if (int rc = front_msm(m, st, fast != 0, joint != 0, &ctx->prof)) return rc;
+  point_out(st, d_r, (int)n1, d_o);
+  point_out(st, d_r2, 1, d_o + n1 * 16);
+  HIP_TRY(hipGetLastError(), where);
+  HIP_TRY(hipMemcpyAsync(out_g1, d_o, n1 * 64, hipMemcpyDeviceToHost, st), where);
+  HIP_TRY(hipMemcpyAsync(out_g2, d_o + n1 * 16, 128, hipMemcpyDeviceToHost, st), where);
+  HIP_TRY(hipStreamSynchronize(st), where);
   return ZKFL_OK;
 }
 

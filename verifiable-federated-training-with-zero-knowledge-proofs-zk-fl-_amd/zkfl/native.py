@@ -151,6 +151,11 @@ SIGNATURES = {
     "zkfl_debug_prove_parts": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, _U8P, _U8P]),
     "zkfl_debug_glv_split": (C.c_int, [C.c_char_p, _U8P]),
     "zkfl_debug_g1_glv_mul": (C.c_int, [_P, C.c_size_t, C.c_char_p, C.c_char_p, _U8P]),
+    "zkfl_debug_msm_front": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_char_p),
+                                       C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
+                                       C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32), C.POINTER(C.c_char_p),
+                                       C.POINTER(C.c_size_t), C.c_uint32, C.c_char_p, C.c_size_t, C.c_int, C.c_int,
+                                       _U8P, _U8P]),
     "zkfl_debug_wtrace": (C.c_int, [_P, C.c_int, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
     "zkfl_msm_g1": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_size_t, _U8P]),
     "zkfl_msm_g2": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_size_t, _U8P]),
@@ -454,6 +459,30 @@ class Context(_Handle):
         out = _buf(64 * n)
         check(lib().zkfl_debug_g1_glv_mul(self.h, n, points, scalars, out))
         return bytes(out)
+
+    def msm_front(self, sets, b: int, bases_g2: bytes, fast: bool = True, joint: bool = True):
+        """The MSM stage of a small key's proof on the caller's sets (parity hook,
+        zkfl_debug_msm_front).  sets: 1..4 of (bases, scalars) or (bases, scalars, sidx, extra_start,
+        extra) -- mont affine G1 bases, std scalars, sidx a sequence of u32 (one per base) or None;
+        bases_g2: one mont affine G2 base per base of set b.  -> ([64 B std affine per set], 128 B)."""
+        n1 = len(sets)
+        full = [tuple(s) + (None, 0, b"")[len(s) - 2:] for s in sets]
+        arr = lambda t, v: (t * n1)(*v)
+        maps = [(C.c_uint32 * len(s[2]))(*s[2]) if s[2] is not None else None for s in full]
+        for s, m in zip(full, maps):
+            assert len(s[0]) % 64 == 0 and len(s[1]) % 32 == 0 and len(s[4]) % 32 == 0
+            assert m is None or len(m) == len(s[0]) // 64
+        assert len(bases_g2) % 128 == 0
+        out1, out2 = _buf(64 * n1), _buf(128)
+        check(lib().zkfl_debug_msm_front(
+            self.h, n1, arr(C.c_size_t, [len(s[0]) // 64 for s in full]), arr(C.c_char_p, [s[0] for s in full]),
+            arr(C.c_char_p, [s[1] for s in full]), arr(C.c_size_t, [len(s[1]) // 32 for s in full]),
+            arr(C.POINTER(C.c_uint32), [C.cast(m, C.POINTER(C.c_uint32)) if m is not None else None for m in maps]),
+            arr(C.c_uint32, [s[3] for s in full]), arr(C.c_char_p, [s[4] for s in full]),
+            arr(C.c_size_t, [len(s[4]) // 32 for s in full]), b, bases_g2, len(bases_g2) // 128, int(fast),
+            int(joint), out1, out2))
+        o = bytes(out1)
+        return [o[64 * i:64 * i + 64] for i in range(n1)], bytes(out2)
 
     def msm_g2(self, bases: bytes, scalars: bytes) -> bytes:
         n = len(scalars) // 32
