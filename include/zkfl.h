@@ -323,6 +323,13 @@ int zkfl_debug_wtrace(zkfl_ctx* ctx, int op, uint32_t cap, void* out, uint32_t* 
  * bytes. */
 int zkfl_debug_ntt_coset(zkfl_ctx* ctx, uint8_t* data, uint32_t logn, uint32_t nvec, size_t vstride, int col_max);
 
+/* The polynomial stage's last step on a caller's vectors (parity hook): abc = a | b | c, each 2^logn
+ * (logn 1..27) std-form elements on the domain (3 * 2^logn * 32 bytes), to h_out = a b - c on the odd
+ * coset, 2^logn std-form elements (2^logn * 32 bytes): the batched transform of the three vectors and
+ * the join kernel, the two calls a proof makes, at sizes no proving key has.  col_max: as for
+ * zkfl_debug_ntt_coset.  Every schedule gives the same bytes. */
+int zkfl_debug_coset_join(zkfl_ctx* ctx, const uint8_t* abc, uint32_t logn, int col_max, uint8_t* h_out);
+
 /* Stand-alone primitives (parity tests).  bases: mont affine; scalars: std, n x 32 B. */
 int zkfl_msm_g1(zkfl_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, uint8_t out[64]);
 int zkfl_msm_g2(zkfl_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, uint8_t out[128]);

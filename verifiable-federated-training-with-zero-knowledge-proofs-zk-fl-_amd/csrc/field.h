@@ -12,6 +12,9 @@
 namespace zkfl {
 
 #define ZK_DEV __device__ __forceinline__
+// The element arithmetic below also compiles for the host (tools/fr_check.cpp checks it against big
+// integers on the CPU): the same code, with the column multiply-add in plain C++.
+#define ZK_HD __host__ __device__ __forceinline__
 
 struct FqP {  // base field q
   static constexpr uint32_t P[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u,
@@ -42,7 +45,7 @@ using Fq = Fp<FqP>;
 using Fr = Fp<FrP>;
 
 template <class PR>
-ZK_DEV Fp<PR> fp_zero() {
+ZK_HD Fp<PR> fp_zero() {
   Fp<PR> r;
 #pragma unroll
   for (int i = 0; i < 8; i++) r.v[i] = 0;
@@ -50,7 +53,7 @@ ZK_DEV Fp<PR> fp_zero() {
 }
 
 template <class PR>
-ZK_DEV Fp<PR> fp_one() {  // Montgomery one
+ZK_HD Fp<PR> fp_one() {  // Montgomery one
   Fp<PR> r;
 #pragma unroll
   for (int i = 0; i < 8; i++) r.v[i] = PR::ONE[i];
@@ -58,7 +61,7 @@ ZK_DEV Fp<PR> fp_one() {  // Montgomery one
 }
 
 template <class PR>
-ZK_DEV bool fp_is_zero(const Fp<PR>& a) {
+ZK_HD bool fp_is_zero(const Fp<PR>& a) {
   uint32_t x = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) x |= a.v[i];
@@ -66,7 +69,7 @@ ZK_DEV bool fp_is_zero(const Fp<PR>& a) {
 }
 
 template <class PR>
-ZK_DEV bool fp_eq(const Fp<PR>& a, const Fp<PR>& b) {
+ZK_HD bool fp_eq(const Fp<PR>& a, const Fp<PR>& b) {
   uint32_t x = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) x |= a.v[i] ^ b.v[i];
@@ -75,7 +78,7 @@ ZK_DEV bool fp_eq(const Fp<PR>& a, const Fp<PR>& b) {
 
 // r = a - p if a >= p else a   (a < 2p)
 template <class PR>
-ZK_DEV void fp_reduce_once(uint32_t r[8], const uint32_t a[8]) {
+ZK_HD void fp_reduce_once(uint32_t r[8], const uint32_t a[8]) {
   uint32_t t[8];
   uint32_t borrow = 0;
 #pragma unroll
@@ -89,7 +92,7 @@ ZK_DEV void fp_reduce_once(uint32_t r[8], const uint32_t a[8]) {
 }
 
 template <class PR>
-ZK_DEV Fp<PR> fp_add(const Fp<PR>& a, const Fp<PR>& b) {
+ZK_HD Fp<PR> fp_add(const Fp<PR>& a, const Fp<PR>& b) {
   uint32_t s[8];
   uint64_t c = 0;
 #pragma unroll
@@ -104,7 +107,7 @@ ZK_DEV Fp<PR> fp_add(const Fp<PR>& a, const Fp<PR>& b) {
 }
 
 template <class PR>
-ZK_DEV Fp<PR> fp_sub(const Fp<PR>& a, const Fp<PR>& b) {
+ZK_HD Fp<PR> fp_sub(const Fp<PR>& a, const Fp<PR>& b) {
   uint32_t d[8];
   uint32_t borrow = 0;
 #pragma unroll
@@ -127,12 +130,12 @@ ZK_DEV Fp<PR> fp_sub(const Fp<PR>& a, const Fp<PR>& b) {
 }
 
 template <class PR>
-ZK_DEV Fp<PR> fp_neg(const Fp<PR>& a) {
+ZK_HD Fp<PR> fp_neg(const Fp<PR>& a) {
   return fp_sub<PR>(fp_zero<PR>(), a);
 }
 
 template <class PR>
-ZK_DEV Fp<PR> fp_dbl(const Fp<PR>& a) {
+ZK_HD Fp<PR> fp_dbl(const Fp<PR>& a) {
   return fp_add<PR>(a, a);
 }
 
@@ -146,6 +149,7 @@ ZK_DEV Fp<PR> fp_dbl(const Fp<PR>& a) {
 // the MSM kernel's 4 waves/SIMD 118 G/s with the SGPR carry vs 109 G/s with the carry pinned
 // to VCC (a fixed VCC clobber serializes independent multiplications).  Both moduli are 254-bit
 // so the column accumulator never exceeds 3 words.
+#if defined(__HIP_DEVICE_COMPILE__)
 #define ZK_MAC_VV(lo, hi, x, y)                                                                             \
   do {                                                                                                      \
     uint64_t cc_;                                                                                           \
@@ -158,9 +162,18 @@ ZK_DEV Fp<PR> fp_dbl(const Fp<PR>& a) {
     asm("v_mad_u64_u32 %0, %1, %3, %4, %0\n\tv_addc_co_u32 %2, %1, %2, 0, %1" : "+v"(lo), "=&s"(cc_), "+v"(hi) \
         : "v"(x), "s"(y));                                                                                  \
   } while (0)
+#else
+#define ZK_MAC_VV(lo, hi, x, y)                       \
+  do {                                                \
+    const uint64_t p_ = (uint64_t)(x) * (uint64_t)(y); \
+    lo += p_;                                         \
+    hi += lo < p_;                                    \
+  } while (0)
+#define ZK_MAC_VS(lo, hi, x, y) ZK_MAC_VV(lo, hi, x, y)
+#endif
 
 template <class PR>
-ZK_DEV Fp<PR> fp_mul(const Fp<PR>& a, const Fp<PR>& b) {
+ZK_HD Fp<PR> fp_mul(const Fp<PR>& a, const Fp<PR>& b) {
   uint32_t m[8], u[9];
   uint64_t lo = 0;
   uint32_t hi = 0;
@@ -199,7 +212,7 @@ ZK_DEV Fp<PR> fp_mul(const Fp<PR>& a, const Fp<PR>& b) {
 // accumulator holds it); a*b + c*d < 2p^2 < 2^256 p, so the result is < 2p before the final
 // subtraction.  200 multiply-adds instead of 2 x 136 (FqOps::mul_sub).
 template <class PR>
-ZK_DEV Fp<PR> fp_mul_sum2(const Fp<PR>& a, const Fp<PR>& b, const Fp<PR>& c, const Fp<PR>& d) {
+ZK_HD Fp<PR> fp_mul_sum2(const Fp<PR>& a, const Fp<PR>& b, const Fp<PR>& c, const Fp<PR>& d) {
   uint32_t m[8], u[9];
   uint64_t lo = 0;
   uint32_t hi = 0;
@@ -237,13 +250,13 @@ ZK_DEV Fp<PR> fp_mul_sum2(const Fp<PR>& a, const Fp<PR>& b, const Fp<PR>& c, con
 }
 
 template <class PR>
-ZK_DEV Fp<PR> fp_sqr(const Fp<PR>& a) {
+ZK_HD Fp<PR> fp_sqr(const Fp<PR>& a) {
   return fp_mul<PR>(a, a);
 }
 
 // Standard <-> Montgomery
 template <class PR>
-ZK_DEV Fp<PR> fp_to_mont(const Fp<PR>& a) {
+ZK_HD Fp<PR> fp_to_mont(const Fp<PR>& a) {
   Fp<PR> r2;
 #pragma unroll
   for (int i = 0; i < 8; i++) r2.v[i] = PR::R2[i];
@@ -251,7 +264,7 @@ ZK_DEV Fp<PR> fp_to_mont(const Fp<PR>& a) {
 }
 
 template <class PR>
-ZK_DEV Fp<PR> fp_from_mont(const Fp<PR>& a) {
+ZK_HD Fp<PR> fp_from_mont(const Fp<PR>& a) {
   Fp<PR> one;
   one.v[0] = 1;
 #pragma unroll

@@ -52,29 +52,33 @@ __global__ void __launch_bounds__(64) k_group_sums(const Affine<F>* __restrict__
   out[j] = xyzz_to_affine<F>(acc);
 }
 
-constexpr int DELTA_T = 256;
+constexpr int DELTA_T = 256, DELTA_BLOCKS_MAX = 512;  // at most two blocks per CU of an MI355X
 
 __global__ void __launch_bounds__(DELTA_T) k_group_delta(const Fr* __restrict__ w, const uint32_t* __restrict__ rep,
                                                          uint32_t n, Fr* __restrict__ u, uint32_t* __restrict__ cnt,
                                                          uint32_t* __restrict__ miss_out, const GroupMark M) {
   ZK_LIGHT();
-  const uint32_t i = blockIdx.x * DELTA_T + threadIdx.x;
-  int nz = 0;
-  if (i < n) {
-    const uint32_t r = rep[i];
-    Fr v = fp_zero<FrP>();
-    if (r != i) {
-      v = fp_sub(w[i], w[r]);
+  // grid-stride over whole blocks of wires (b0 is the same in every thread of the block, so its
+  // waves enter and leave the loop together): a few hundred blocks end on the two counters below,
+  // not one per 256 wires
+  int blk = 0;
+  for (uint32_t b0 = blockIdx.x * DELTA_T; b0 < n; b0 += gridDim.x * DELTA_T) {
+    const uint32_t i = b0 + threadIdx.x;
+    int nz = 0;
+    if (i < n) {
+      const uint32_t r = rep[i];
+      Fr v = fp_zero<FrP>();
+      if (r != i) {
+        v = fp_sub(w[i], w[r]);
 #pragma unroll
-      for (int k = 0; k < 8; k++) nz |= v.v[k] != 0;
+        for (int k = 0; k < 8; k++) nz |= v.v[k] != 0;
+      }
+      u[i] = v;
     }
-    u[i] = v;
-  }
-  if (M.wstart) {
-    // grouped ABC: the missing wires go to the slot's list, one atomic per wave that has any;
-    // k_group_mark walks their constraint lists (or raises the plain flag when there are too many)
     const unsigned long long m = __ballot(nz);
-    if (m) {
+    if (m && M.wstart) {
+      // grouped ABC: the missing wires go to the slot's list, one atomic per wave that has any;
+      // k_group_mark walks their constraint lists (or raises the plain flag when there are too many)
       const uint32_t lane = threadIdx.x & (warpSize - 1);
       const int first = __ffsll((long long)m) - 1;
       uint32_t base = 0;
@@ -83,9 +87,16 @@ __global__ void __launch_bounds__(DELTA_T) k_group_delta(const Fr* __restrict__ 
       const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
       if (nz && at < M.miss_cap) M.missing[at] = i;
     }
+    blk += nz;
   }
-  const int blk = __syncthreads_count(nz);
+  // the block's misses: lane sums folded per wave, the waves' sums through LDS
+  __shared__ int wave_nz[DELTA_T / 64];
+  for (int off = warpSize / 2; off; off >>= 1) blk += __shfl_xor(blk, off);
+  if ((threadIdx.x & (warpSize - 1)) == 0) wave_nz[threadIdx.x / warpSize] = blk;
+  __syncthreads();
   if (threadIdx.x == 0) {
+    blk = 0;
+    for (int k = 0; k < DELTA_T / warpSize; k++) blk += wave_nz[k];
     // the last block to arrive publishes the total and leaves both counters zero for the next launch
     if (blk) atomicAdd(&cnt[0], (uint32_t)blk);
     __threadfence();
@@ -141,7 +152,8 @@ template void group_sums<Fq2Ops>(hipStream_t, const G2Aff*, int, size_t, const u
 
 void group_delta(hipStream_t st, const Fr* w, const uint32_t* rep, uint32_t n, Fr* u, uint32_t* cnt,
                  uint32_t* miss_out, const GroupMark& mark) {
-  hipLaunchKernelGGL(k_group_delta, dim3(zk_grid(n, DELTA_T)), dim3(DELTA_T), 0, st, w, rep, n, u, cnt, miss_out, mark);
+  const unsigned blocks = std::min<unsigned>(zk_grid(n, DELTA_T), DELTA_BLOCKS_MAX);
+  hipLaunchKernelGGL(k_group_delta, dim3(blocks), dim3(DELTA_T), 0, st, w, rep, n, u, cnt, miss_out, mark);
 }
 
 void group_mark_rows(hipStream_t st, const GroupMark& mark) {

@@ -78,9 +78,41 @@ __global__ void k_ntt_dit_stage(Fr* __restrict__ a, size_t n, size_t half, const
   x[i1] = fp_sub(u, w);
 }
 
+// One radix-2 stage of span `half` >= 2 over an LDS tile of 2 * nbf elements (the caller's barrier
+// follows).  tw[0] is the Montgomery one exactly (k_ntt_twiddles) and every value a tile holds is
+// fully reduced (sums, differences and products of reduced values), so fp_mul by tw[0] returns its
+// operand bit for bit (tests/test_fr_mul_one.py) and the butterflies with j = 0 go without it: all
+// of a span-1 stage (the callers' own steps) and every other butterfly of a span-2 stage.  At span
+// 2 the threads take the j = 0 butterflies first and the j = 1 ones after them, so whole waves skip
+// the product instead of half the lanes of every wave idling through it.
+template <bool DIF>
+ZK_DEV void ntt_lds_stage(Fr* tile, size_t nbf, size_t half, const Fr* __restrict__ tw, size_t twstride) {
+  const size_t hb = nbf >> 1;
+  for (size_t t = threadIdx.x; t < nbf; t += blockDim.x) {
+    const size_t q = half == 2 ? (t < hb ? t << 1 : ((t - hb) << 1) | 1) : t;  // butterfly of this thread
+    const size_t j = q & (half - 1), i0 = ((q - j) << 1) + j, i1 = i0 + half;
+    const Fr u = tile[i0];
+    Fr w = tile[i1];
+    if (half == 2 && j == 0) {
+      tile[i0] = fp_add(u, w);
+      tile[i1] = fp_sub(u, w);
+    } else if (DIF) {
+      tile[i0] = fp_add(u, w);
+      tile[i1] = fp_mul(fp_sub(u, w), tw[j * twstride]);
+    } else {
+      w = fp_mul(w, tw[j * twstride]);
+      tile[i0] = fp_add(u, w);
+      tile[i1] = fp_sub(u, w);
+    }
+  }
+}
+
 // Fused small-span stages inside one LDS tile of T = min(n, 1024) elements.
 //   DIF: spans T/2 .. 1 (the last log2 T stages of the inverse transform)
 //   DIT: spans 1 .. T/2 (the first log2 T stages of the forward transform)
+// The span-1 stage has no product (ntt_lds_stage) and sits at the memory end of the pass, so it
+// runs on the way out (DIF, with the coset scale where one is given) or on the way in (DIT): at
+// T = 2 it is the whole pass.
 template <bool DIF>
 __global__ void __launch_bounds__(512) k_ntt_lds(Fr* __restrict__ a, size_t n, int logt,
                                                  const Fr* __restrict__ tw, int nvec, size_t vstride,
@@ -91,42 +123,48 @@ __global__ void __launch_bounds__(512) k_ntt_lds(Fr* __restrict__ a, size_t n, i
   const size_t tile_id = blockIdx.x;
   const size_t v = tile_id / tiles_per_vec;
   if (v >= (size_t)nvec) return;
-  Fr* x = a + v * vstride + (tile_id - v * tiles_per_vec) * T;
-  for (size_t i = threadIdx.x; i < T; i += blockDim.x) tile[i] = x[i];
-  __syncthreads();
+  const size_t base = (tile_id - v * tiles_per_vec) * T;
+  Fr* x = a + v * vstride + base;
   const size_t nbf = T >> 1;
-  for (int s = 0; s < logt; s++) {
-    const size_t half = DIF ? (T >> (s + 1)) : ((size_t)1 << s);
-    const size_t len = half << 1;
-    const size_t twstride = n / len;
+  if (DIF) {
+    for (size_t i = threadIdx.x; i < T; i += blockDim.x) tile[i] = x[i];
+    __syncthreads();
+    for (int s = 0; s + 1 < logt; s++) {  // spans T/2 .. 2
+      ntt_lds_stage<true>(tile, nbf, T >> (s + 1), tw, n / (T >> s));
+      __syncthreads();
+    }
+    // span 1, and the fused coset scale (inverse pass): x[p] *= inc^bitrev(p) / n
     for (size_t t = threadIdx.x; t < nbf; t += blockDim.x) {
-      size_t j = t & (half - 1);
-      size_t i0 = ((t - j) << 1) + j;
-      size_t i1 = i0 + half;
-      Fr u = tile[i0], w = tile[i1];
-      Fr tws = tw[j * twstride];
-      if (DIF) {
-        tile[i0] = fp_add(u, w);
-        tile[i1] = fp_mul(fp_sub(u, w), tws);
-      } else {
-        w = fp_mul(w, tws);
-        tile[i0] = fp_add(u, w);
-        tile[i1] = fp_sub(u, w);
+      const Fr u = tile[2 * t], w = tile[2 * t + 1];
+      Fr r0 = fp_add(u, w), r1 = fp_sub(u, w);
+      if (scale) {
+        r0 = fp_mul(r0, scale[base + 2 * t]);
+        r1 = fp_mul(r1, scale[base + 2 * t + 1]);
       }
+      x[2 * t] = r0;
+      x[2 * t + 1] = r1;
+    }
+  } else {
+    for (size_t t = threadIdx.x; t < nbf; t += blockDim.x) {  // span 1
+      const Fr u = x[2 * t], w = x[2 * t + 1];
+      tile[2 * t] = fp_add(u, w);
+      tile[2 * t + 1] = fp_sub(u, w);
     }
     __syncthreads();
-  }
-  const size_t base = (tile_id - v * tiles_per_vec) * T;
-  if (scale)  // fused coset scale (inverse pass): x[p] *= inc^bitrev(p) / n
-    for (size_t i = threadIdx.x; i < T; i += blockDim.x) x[i] = fp_mul(tile[i], scale[base + i]);
-  else
+    for (int s = 1; s < logt; s++) {  // spans 2 .. T/2
+      ntt_lds_stage<false>(tile, nbf, (size_t)1 << s, tw, n / ((size_t)2 << s));
+      __syncthreads();
+    }
     for (size_t i = threadIdx.x; i < T; i += blockDim.x) x[i] = tile[i];
+  }
 }
 
 // The inverse transform's LDS pass, the coset scale and the forward transform's LDS pass on
 // the same tile in one kernel (the tiles coincide: both passes take T consecutive elements), so
 // the tile makes one HBM round trip instead of two.  Bit-identical to k_ntt_lds<true> with
-// `scale` followed by k_ntt_lds<false>.
+// `scale` followed by k_ntt_lds<false>.  The two span-1 stages and the scale between them are one
+// step on the pair (2t, 2t + 1) in registers: x = u +- w, y = x * scale, z = y0 +- y1 -- two
+// products and one LDS round trip for what were four products (two by one) and three.
 __global__ void __launch_bounds__(512) k_ntt_lds_pair(Fr* __restrict__ a, size_t n, int logt,
                                                       const Fr* __restrict__ tw_inv, const Fr* __restrict__ tw_fwd,
                                                       int nvec, size_t vstride, const Fr* __restrict__ scale) {
@@ -143,26 +181,19 @@ __global__ void __launch_bounds__(512) k_ntt_lds_pair(Fr* __restrict__ a, size_t
   for (size_t i = threadIdx.x; i < T; i += blockDim.x) tile[i] = x[i];
   __syncthreads();
   const size_t nbf = T >> 1;
-  for (int s = 0; s < logt; s++) {  // DIF, spans T/2 .. 1
-    const size_t half = T >> (s + 1), twstride = n / (half << 1);
-    for (size_t t = threadIdx.x; t < nbf; t += blockDim.x) {
-      const size_t j = t & (half - 1), i0 = ((t - j) << 1) + j, i1 = i0 + half;
-      const Fr u = tile[i0], w = tile[i1];
-      tile[i0] = fp_add(u, w);
-      tile[i1] = fp_mul(fp_sub(u, w), tw_inv[j * twstride]);
-    }
+  for (int s = 0; s + 1 < logt; s++) {  // DIF, spans T/2 .. 2
+    ntt_lds_stage<true>(tile, nbf, T >> (s + 1), tw_inv, n / (T >> s));
     __syncthreads();
   }
-  for (size_t i = threadIdx.x; i < T; i += blockDim.x) tile[i] = fp_mul(tile[i], scale[base + i]);
+  for (size_t t = threadIdx.x; t < nbf; t += blockDim.x) {  // DIF span 1, scale, DIT span 1
+    const Fr u = tile[2 * t], w = tile[2 * t + 1];
+    const Fr y0 = fp_mul(fp_add(u, w), scale[base + 2 * t]), y1 = fp_mul(fp_sub(u, w), scale[base + 2 * t + 1]);
+    tile[2 * t] = fp_add(y0, y1);
+    tile[2 * t + 1] = fp_sub(y0, y1);
+  }
   __syncthreads();
-  for (int s = 0; s < logt; s++) {  // DIT, spans 1 .. T/2
-    const size_t half = (size_t)1 << s, twstride = n / (half << 1);
-    for (size_t t = threadIdx.x; t < nbf; t += blockDim.x) {
-      const size_t j = t & (half - 1), i0 = ((t - j) << 1) + j, i1 = i0 + half;
-      const Fr u = tile[i0], w = fp_mul(tile[i1], tw_fwd[j * twstride]);
-      tile[i0] = fp_add(u, w);
-      tile[i1] = fp_sub(u, w);
-    }
+  for (int s = 1; s < logt; s++) {  // DIT, spans 2 .. T/2
+    ntt_lds_stage<false>(tile, nbf, (size_t)1 << s, tw_fwd, n / ((size_t)2 << s));
     __syncthreads();
   }
   for (size_t i = threadIdx.x; i < T; i += blockDim.x) x[i] = tile[i];

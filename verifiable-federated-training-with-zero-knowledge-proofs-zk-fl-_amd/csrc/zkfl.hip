@@ -415,6 +415,32 @@ int zkfl_ntt_coset(zkfl_ctx* ctx, uint8_t* data, uint32_t logn) {
   return zkfl_debug_ntt_coset(ctx, data, logn, 1, logn <= 27 ? (size_t)1 << logn : 0, -1);
 }
 
+int zkfl_debug_coset_join(zkfl_ctx* ctx, const uint8_t* abc, uint32_t logn, int col_max, uint8_t* h_out) {
+  if (!ctx || !abc || !h_out || logn < 1 || logn > 27 || col_max > NTT_COL_TILE_LOG)
+    return fail(ZKFL_E_ARG, "coset join: bad args");
+  const size_t n = (size_t)1 << logn;
+  hipStream_t st = ctx->st;
+  struct Plan {  // released on every exit path
+    NttPlan pl;
+    ~Plan() { ntt_plan_free(pl); }
+  } P;
+  DevBufs D;
+  Fr *d, *h;
+  HIP_TRY(ntt_plan_alloc(P.pl, (int)logn, st), "coset join");
+  if (col_max >= 0) P.pl.col_max = col_max;
+  HIP_TRY(D.get(&d, 3 * n), "coset join");
+  HIP_TRY(D.get(&h, n), "coset join");
+  HIP_TRY(hipMemcpyAsync(d, abc, 3 * n * 32, hipMemcpyHostToDevice, st), "coset join");
+  fr_std_to_mont(st, d, 3 * n);
+  // the prover's own two calls (abc_ntt, csrc/prove.hip)
+  HIP_TRY(ntt_coset_shift(P.pl, d, 3, n, st), "coset join");
+  join_h(st, d, n, h);
+  HIP_TRY(hipGetLastError(), "coset join");
+  HIP_TRY(hipMemcpyAsync(h_out, h, n * 32, hipMemcpyDeviceToHost, st), "coset join");
+  HIP_TRY(hipStreamSynchronize(st), "coset join");
+  return ZKFL_OK;
+}
+
 // Ceremony primitives (csrc/setup.hip)
 static int setup_gen_mul_abi(zkfl_ctx* ctx, const uint8_t* scalars, size_t n, uint8_t* out, bool g2) {
   if (!ctx || !scalars || !out) return fail(ZKFL_E_ARG, "gen_mul: bad args");

@@ -161,6 +161,7 @@ SIGNATURES = {
     "zkfl_msm_g2": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_size_t, _U8P]),
     "zkfl_ntt_coset": (C.c_int, [_P, _U8P, C.c_uint32]),
     "zkfl_debug_ntt_coset": (C.c_int, [_P, _U8P, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int]),
+    "zkfl_debug_coset_join": (C.c_int, [_P, C.c_char_p, C.c_uint32, C.c_int, _U8P]),
     "zkfl_setup_g1_gen_mul": (C.c_int, [_P, C.c_char_p, C.c_size_t, _U8P]),
     "zkfl_setup_g2_gen_mul": (C.c_int, [_P, C.c_char_p, C.c_size_t, _U8P]),
     "zkfl_setup_g1_scale": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_size_t, _U8P]),
@@ -510,6 +511,16 @@ class Context(_Handle):
         buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
         check(lib().zkfl_debug_ntt_coset(self.h, buf, logn, nvec, vstride, col_max))
         return bytes(buf)
+
+    def debug_coset_join(self, abc: bytes, logn: int, col_max: int = -1) -> bytes:
+        """h = a b - c on the odd coset (std form) from abc = a | b | c on the domain, 2^logn elements
+        each, by the prover's own transform and join (parity hook, zkfl_debug_coset_join); col_max as
+        for debug_ntt_coset."""
+        n = 1 << logn
+        assert len(abc) == 3 * n * 32
+        out = _buf(32 * n)
+        check(lib().zkfl_debug_coset_join(self.h, abc, logn, col_max, out))
+        return bytes(out)
 
     def g1_gen_mul(self, scalars: bytes) -> bytes:
         n = len(scalars) // 32
