@@ -79,7 +79,8 @@ int zkfl_ctx_set_profiling(zkfl_ctx* ctx, int enabled);
  * "keycheck_points", "keycheck_rows", "keycheck_msm", "keycheck_pairing" (the key check's stages),
  * "ptaucheck_points", "ptaucheck_scalars", "ptaucheck_msm", "ptaucheck_pairing" (the ptau check's
  * stages, one record per chunk pass; units: points),
- * "secagg_terms", "secagg_fold" (the mask engine's two kernels; units: hashes, output values).
+ * "secagg_terms", "secagg_fold" (the mask engine's two kernels; units: hashes, output values),
+ * "admit_chunks", "admit_clients" (the admission checks' two passes; units: chunk hashes, clients).
  * Synchronises the device.
  * total_ms: summed event time; units: summed algorithmic units (MSM entries, NTT elements...);
  * median_ms (nullable): median single-launch time, robust to a one-off stalled dispatch. */
@@ -750,6 +751,110 @@ int zkfl_secagg_aggregate(zkfl_ctx* ctx, size_t n_groups, uint32_t dim, const ui
                           const uint8_t* masked, const uint64_t* pair_ptr, const uint64_t* pair_in,
                           const uint64_t* pair_out, const uint8_t* pair_keys, const uint8_t round[32],
                           uint8_t* sum_out, int64_t* signed_out, uint8_t* out_of_range, uint32_t chunk_terms);
+
+/* Admitting a round: the checks the reference's server runs on a client's three packages before
+ * each `groth16 verify` (the Server class of tests/full_system_simulation.mjs: verifyBalanceProof
+ * :848-880, verifyTrainingProof :886-990, verifySecureAggregationProof :995-1131), the proofs that pass
+ * them verified, and one code per client and phase (csrc/admit.hip).  A code is 0 (accepted) or the
+ * first failing check in the reference's order, which is the order of the values below.  *_MISSING
+ * is for a client whose package of that phase is absent (the reference has no such case: every
+ * client sends).  The reference's "no balance proof" test at :1018-1023 cannot fire once the
+ * training proof is accepted, so it has no code.  Like the reference, the balance phase does not
+ * look at client_id, N_public, c0 or c1, and training signal 0 is not compared with the client id:
+ * it is bound through root_G. */
+#define ZKFL_ADMIT_OK 0
+#define ZKFL_ADMIT_B_MISSING 1         /* no balance package */
+#define ZKFL_ADMIT_B_SIG_ROOT_D 2      /* public signal 1 != claimed root_D (:853-858) */
+#define ZKFL_ADMIT_B_PROOF 3           /* the proof does not verify (:865-874) */
+#define ZKFL_ADMIT_T_MISSING 16        /* no training package */
+#define ZKFL_ADMIT_T_NO_BALANCE 17     /* the balance code is not 0 (:895-900) */
+#define ZKFL_ADMIT_T_BIND_ROOT_D 18    /* claimed root_D != the balance package's (:902-908) */
+#define ZKFL_ADMIT_T_SIG_ROOT_D 19     /* signal 2 != claimed root_D (:920-924) */
+#define ZKFL_ADMIT_T_SIG_ROOT_G 20     /* signal 3 != claimed root_G (:926-930) */
+#define ZKFL_ADMIT_T_SIG_ROOT_W 21     /* signal 4 != claimed root_W (:932-936) */
+#define ZKFL_ADMIT_T_SIG_ROUND 22      /* signal 1 != the package's round (:938-942) */
+#define ZKFL_ADMIT_T_ROUND_STALE 23    /* ZKFL_ADMIT_CHECK_ROUND: the package's round != the server's */
+#define ZKFL_ADMIT_T_SIG_TAU 24        /* signal 5 != the server's tauSquared (:945-950) */
+#define ZKFL_ADMIT_T_ROOT_G_GRADIENT 25 /* gradientCommitment(gradient, id, round) != claimed root_G (:953-965, :139-164) */
+#define ZKFL_ADMIT_T_ROOT_W_MODEL 26   /* ZKFL_ADMIT_CHECK_MODEL: claimed root_W != weightCommitment(weights) (:168-170) */
+#define ZKFL_ADMIT_T_PROOF 27          /* the proof does not verify (:975-984) */
+#define ZKFL_ADMIT_S_MISSING 32        /* no secagg package */
+#define ZKFL_ADMIT_S_NO_TRAINING 33    /* the training code is not 0 (:1003-1008) */
+#define ZKFL_ADMIT_S_BIND_ROOT_G 34    /* claimed root_G != the training package's (:1010-1014) */
+#define ZKFL_ADMIT_S_BIND_ROOT_D 35    /* claimed root_D != the balance package's (:1024-1028) */
+#define ZKFL_ADMIT_S_BIND_ROOT_W 36    /* claimed root_W != the training package's (:1032-1036) */
+#define ZKFL_ADMIT_S_SIG_CLIENT_ID 37  /* signal 0 != the client's id (:1050-1054) */
+#define ZKFL_ADMIT_S_SIG_ROUND 38      /* signal 1 != the package's round (:1057-1061) */
+#define ZKFL_ADMIT_S_ROUND_STALE 39    /* ZKFL_ADMIT_CHECK_ROUND: the package's round != the server's */
+#define ZKFL_ADMIT_S_SIG_ROOT_D 40     /* signal 2 != claimed root_D (:1065-1069) */
+#define ZKFL_ADMIT_S_SIG_ROOT_G 41     /* signal 3 != claimed root_G (:1072-1076) */
+#define ZKFL_ADMIT_S_SIG_ROOT_W 42     /* signal 4 != claimed root_W (:1079-1083) */
+#define ZKFL_ADMIT_S_SIG_ROOT_K 43     /* signal 5 != claimed root_K (:1086-1090) */
+#define ZKFL_ADMIT_S_SIG_TAU 44        /* signal 6 != the server's tauSquared (:1093-1097) */
+#define ZKFL_ADMIT_S_SIG_MASKED 45     /* some signal 7 + k != masked_update[k] (:1101-1108) */
+#define ZKFL_ADMIT_S_SIG_PEERS 46      /* ZKFL_ADMIT_CHECK_PEERS: signals 7 + dim.. are not the listed peer ids */
+#define ZKFL_ADMIT_S_PROOF 47          /* the proof does not verify (:1116-1125) */
+/* Flags.  The three checks the reference lacks; with all three clear the verdicts are the
+ * reference's exactly.
+ *   CHECK_ROUND  a package's round must be the server's (the reference compares a package only with
+ *                itself; zkfl's aggregate-round already refuses a disagreeing round);
+ *   CHECK_MODEL  the training root_W must be weightCommitment(weights), computed once per call;
+ *   CHECK_PEERS  signals 7 + dim.. (peer_ids, public in src/circuits/secure_masked_update.circom:350-360)
+ *                must be exactly peer_ids[peer_ptr[i] .. peer_ptr[i+1]), in that order;
+ *   COMBINED     the proofs go to zkfl_groth16_verify_round instead of zkfl_groth16_verify_multi. */
+#define ZKFL_ADMIT_CHECK_ROUND 1u
+#define ZKFL_ADMIT_CHECK_MODEL 2u
+#define ZKFL_ADMIT_CHECK_PEERS 4u
+#define ZKFL_ADMIT_COMBINED 8u
+#define ZKFL_ADMIT_MAX_DIM 256 /* the limit of zkfl_vector_hash_batch */
+/* One phase of a round, row i belonging to client i.  The rows of a client whose present byte is 0
+ * are ignored (they may hold anything); present NULL: every client sent.
+ * claimed: the package's fields, 32 B std-form LE each, `fields` per client:
+ *   balance   root_D                                   (1)
+ *   training  root_D | root_G | root_W | round         (4)
+ *   secagg    root_D | root_G | root_W | root_K | round (5)
+ * signals: n x nPublic x 32 B, the proof's public signals (balance 5, training 6, secagg
+ * 7 + dim + peers, the peer count of a key being its nPublic - 7 - dim); proofs: n x 256 B. */
+typedef struct {
+  const uint8_t* present;
+  const uint8_t* claimed;
+  const uint8_t* signals;
+  const uint8_t* proofs;
+} zkfl_admit_phase;
+typedef struct {
+  size_t n;                   /* clients */
+  uint32_t dim;               /* 1..ZKFL_ADMIT_MAX_DIM */
+  const uint64_t* ids;        /* n client ids */
+  const uint8_t* round;       /* 32 B: the server's round */
+  const uint8_t* tau_squared; /* 32 B: the server's clipping bound */
+  const zkfl_vkey* vkeys[3];  /* balance, training, secagg */
+  zkfl_admit_phase balance, training, secagg;
+  const int64_t* gradients;     /* n x dim, signed: a negative g stands for r - |g| */
+  const uint8_t* masked_update; /* n x dim x 32 B, the secagg package's */
+  const uint8_t* weights;       /* dim x 32 B, or NULL without CHECK_MODEL */
+  const uint64_t* peer_ptr;     /* n + 1 (CSR, as zkfl_secagg_mask), or NULL without CHECK_PEERS */
+  const uint64_t* peer_ids;
+} zkfl_admit_round;
+/* codes: 3 x n, phase-major (balance, training, secagg).  Everything but the *_PROOF codes and the two
+ * *_NO_* rules is decided by one pass on the device (the static codes); the present packages whose
+ * static code is 0 are verified in one call; then per client the training code is T_MISSING, else
+ * T_NO_BALANCE when the balance code is not 0, else its static code, else the proof's verdict, and
+ * secagg likewise over the training code.  A statically rejected proof is not verified, as in the
+ * reference; a training proof whose balance proof fails its pairing is verified although the
+ * reference would stop before it -- the code is T_NO_BALANCE either way.
+ * report (nullable): the round verifier's under COMBINED, else zero but for `combined`, the number
+ * of proofs verified.
+ * Errors, before any device work, the message naming the index, codes and report untouched:
+ * ZKFL_E_ARG for a value >= r in a present row (or in round, tau_squared, weights), dim == 0 or
+ * dim > ZKFL_ADMIT_MAX_DIM, a flag whose optional input is NULL, a peer_ptr that does not start at 0
+ * or decreases; ZKFL_E_MISMATCH for a key whose nPublic does not fit its phase.  n == 0 is valid. */
+int zkfl_round_admit(zkfl_ctx* ctx, const zkfl_admit_round* in, uint32_t flags, uint32_t* codes,
+                     zkfl_round_report* report);
+/* Parity hook: the static codes alone (3 x n, phase-major; *_PROOF and *_NO_* never appear; a
+ * binding check against an absent package is skipped).  vkeys and proofs are not read;
+ * secagg_npublic stands for the secagg key's nPublic. */
+int zkfl_debug_admit_static(zkfl_ctx* ctx, const zkfl_admit_round* in, uint32_t flags, uint32_t secagg_npublic,
+                            uint32_t* codes);
 
 /* Dev-ceremony fixed-base multiplications: out[i] = scalars[i] * generator, mont affine. */
 int zkfl_setup_g1_gen_mul(zkfl_ctx* ctx, const uint8_t* scalars, size_t n, uint8_t* out);

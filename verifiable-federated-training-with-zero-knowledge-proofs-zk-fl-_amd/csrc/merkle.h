@@ -39,6 +39,11 @@ hipError_t poseidon_batch(const PosTables* P, uint32_t arity, size_t n, const Fr
 // ceil(len/16) Fr when len > 16.
 hipError_t vector_hash_batch(const PosTables* P, uint32_t len, size_t n, const Fr* in, Fr* out, bool out_mont,
                              Fr* scratch, hipStream_t st);
+// poseidon_batch with strides and a choice of forms: out[i * out_stride] = Poseidon(in[i * in_stride
+// .. + arity)); in / out Montgomery when in_mont / out_mont, else std.  The launch vector_hash_batch
+// makes per chunk, for a unit that lays a vector hash out itself (csrc/admit.hip).
+hipError_t poseidon_rows(const PosTables* P, uint32_t arity, size_t n, const Fr* in, size_t in_stride, bool in_mont,
+                         Fr* out, size_t out_stride, bool out_mont, hipStream_t st);
 
 // buildMerkleTree over n Montgomery-form leaves (device) padded to 2^depth with Poseidon([0]):
 // tree_std receives the full padded levels in standard form, level 0 (2^depth) first, root last

@@ -368,6 +368,12 @@ hipError_t vector_hash_batch(const PosTables* P, uint32_t len, size_t n, const F
   return rows_of_arity(P->w, nch, n, scratch, nch, true, out, 1, out_mont, st);
 }
 
+hipError_t poseidon_rows(const PosTables* P, uint32_t arity, size_t n, const Fr* in, size_t in_stride, bool in_mont,
+                         Fr* out, size_t out_stride, bool out_mont, hipStream_t st) {
+  if (arity < 1 || arity > POS_MAX_ARITY) return hipErrorInvalidValue;
+  return rows_of_arity(P->w, arity, n, in, in_stride, in_mont, out, out_stride, out_mont, st);
+}
+
 size_t merkle_work_size(size_t n, uint32_t depth) {
   size_t total = 0;
   (void)level_map(n, depth, &total);

@@ -46,6 +46,27 @@
         is still in it), 2 on a manifest of another shape, a missing file, a public.json whose client_id
         or round disagrees with the manifest, a missing key or a key that is not needed (all decided
         before the GPU is touched)
+    python -m zkfl admit-round <round.json>                  the server's decision between the two: the checks of
+        verifyBalanceProof, verifyTrainingProof and verifySecureAggregationProof (:848-1131) before each
+        `groth16 verify`, the proofs that pass them verified, in one call (zkfl/admit.py).  round.json:
+        {"round", "tau_squared", "dim", "vkeys": {"balance", "training", "secagg": vkey.json paths},
+        "weights": [dim values] (optional), "groups": [{"clients": [{"id", "balance": {"proof", "public",
+        "root_D"}, "training": {"proof", "public", "root_D", "root_G", "root_W", "round", "gradient": [dim
+        signed integers]}, "secagg": {"proof", "public", "root_D", "root_G", "root_W", "root_K", "round",
+        "masked_update": [dim values]}, "peers": [ids] (optional)}], "revealed": [{"in", "out", "key"}]
+        (optional)}]}; "proof" and "public" are proof.json / public.json paths (relative ones are taken
+        from the manifest's directory), a client may lack any of its three packages, and a client's
+        peers default to the other clients of its group in the group's order.  Prints one line per client
+        and phase, `client <id> <phase>: OK` or the name of the first failing check (ZKFL_ADMIT_*,
+        include/zkfl.h); exit 0 if every present package is accepted, 1 otherwise, 2 on a manifest of
+        another shape, a missing file or a value that is not a canonical field element (decided before
+        the GPU is touched)
+        --reference: only the reference's checks (not: a package's round is the server's, root_W commits
+        to "weights", the secagg proof's peer ids are the group's)
+        --combined: as for verify-round
+        --aggregate: then close each group over the clients whose secagg code is 0 (their masked updates
+        are signals 7..7+dim of their public.json) with the group's "revealed" keys, and print
+        aggregate-round's lines; a group without an accepted client prints "sum": null
 
 <circuit> is one of zkfl.circuits.CIRCUITS (poseidon_hash2, sgd_verified, sgd_step_v5,
 balance_unified, secure_masked_update) followed by its integer template parameters.  GPU
@@ -319,6 +340,113 @@ def cmd_aggregate_round(args):
     return 1 if any(s["out_of_range"] for s in sums) else 0
 
 
+def _admit_manifest(path):
+    """round.json of `admit-round` -> (the round dict of zkfl/admit.py, its packed arrays, the groups'
+    rosters and revealed keys), or None with a message on stderr.  Host only."""
+    from . import admit
+
+    def bad(msg):
+        print(f"[ERROR] zkfl: {path}: {msg}", file=sys.stderr)
+
+    try:
+        with open(path) as f:
+            man = json.load(f)
+    except (OSError, ValueError) as e:
+        return bad(e)
+    shape = ('expected {"round", "tau_squared", "dim", "vkeys": {"balance", "training", "secagg"}, '
+             '"groups": [{"clients": [{"id", "balance", "training", "secagg"}]}]} (python -m zkfl --help)')
+    base = os.path.dirname(os.path.abspath(path))
+
+    def load(rel):
+        if not isinstance(rel, str):
+            raise ValueError(shape)
+        full = os.path.join(base, rel)
+        if not os.path.isfile(full):
+            raise ValueError(f"no such file: {full}")
+        try:
+            with open(full) as f:
+                return json.load(f)
+        except ValueError as e:
+            raise ValueError(f"{full}: {e}") from None
+
+    try:
+        if not isinstance(man, dict) or not isinstance(man["groups"], list):
+            return bad(shape)
+        rnd = {"round": man["round"], "tau_squared": man["tau_squared"], "dim": man["dim"], "clients": [],
+               "vkeys": {p: load(man["vkeys"][p]) for p in admit.PHASES},
+               "balance": {}, "training": {}, "secagg": {}, "peers": {}}
+        if man.get("weights") is not None:
+            rnd["weights"] = man["weights"]
+        groups = []
+        for grp in man["groups"]:
+            roster = [int(c["id"]) for c in grp["clients"]]
+            revealed = [(int(t["in"]), int(t["out"]), int(t["key"])) for t in grp.get("revealed", [])]
+            if not all(0 <= t[2] < zkey.R for t in revealed):
+                return bad("a revealed key is not a field element")
+            for c in grp["clients"]:
+                cid = int(c["id"])
+                rnd["clients"].append(cid)
+                rnd["peers"][cid] = c["peers"] if c.get("peers") is not None else [j for j in roster if j != cid]
+                for p in admit.PHASES:
+                    if c.get(p) is None:
+                        continue
+                    pkg = dict(c[p])
+                    pkg["proof"], pkg["publicSignals"] = load(pkg.get("proof")), load(pkg.pop("public", None))
+                    rnd[p][cid] = pkg
+            groups.append((roster, revealed))
+        packed = admit.pack(rnd)
+        for p in admit.PHASES:
+            groth16.vk_bytes(rnd["vkeys"][p])
+    except ValueError as e:
+        return bad(e)
+    except (KeyError, TypeError, AttributeError, AssertionError):
+        return bad(shape)
+    return rnd, packed, groups
+
+
+def cmd_admit_round(args):
+    man = _admit_manifest(args.round)
+    if man is None:
+        return 2
+    from . import admit, secagg
+    rnd, packed, groups = man
+    p = groth16.Prover(int(os.environ.get("LOCAL_RANK", "0")))
+    try:
+        res = admit.admit_round(p, rnd, reference=args.reference, combined=args.combined, packed=packed)
+        if args.combined:
+            print("[INFO]  zkfl: combined round: " + ", ".join(f"{k} {v}" for k, v in res.report.items()),
+                  file=sys.stderr)
+        for cid, names in res.names.items():
+            for phase, name in zip(admit.PHASES, names):
+                print(f"client {cid} {phase}: {name}")
+        rc = 0 if all(c == 0 or native.ADMIT_CODES[c].endswith("_MISSING")
+                      for cs in res.codes.values() for c in cs) else 1
+        if args.aggregate:
+            dim, ok = int(rnd["dim"]), set(res.accepted)
+            todo = []
+            for g, (roster, revealed) in enumerate(groups):
+                acc = {c: [int(x) for x in rnd["secagg"][c]["publicSignals"][7:7 + dim]] for c in roster if c in ok}
+                if acc:
+                    todo.append((g, {"roster": roster, "accepted": acc, "revealed": revealed}))
+            try:
+                sums = dict(zip((g for g, _ in todo),
+                                secagg.close_groups(p.ctx, [grp for _, grp in todo], int(rnd["round"]))))
+            except ValueError as e:
+                print(f"[ERROR] zkfl: {args.round}: {e}", file=sys.stderr)
+                return 1
+            for g in range(len(groups)):
+                s = sums.get(g)
+                line = {"group": g, "clients": s["clients"] if s else 0, "sum": s["sum"] if s else None,
+                        "mean": None if not s or s["sum"] is None else [x / s["clients"] for x in s["sum"]]}
+                if s and s["out_of_range"]:
+                    line["out_of_range"] = True
+                    rc = 1
+                print(json.dumps(line))
+    finally:
+        p.close()
+    return rc
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     if snarkjs_cli.routes(argv):   # snarkjs ceremony strings and `wtns check` (zkfl/snarkjs_cli.py)
@@ -367,11 +495,18 @@ def main(argv=None):
                     help="one random combination and one final exponentiation for the whole round")
     sp = sub.add_parser("aggregate-round")
     sp.add_argument("round")
+    sp = sub.add_parser("admit-round")
+    sp.add_argument("round")
+    sp.add_argument("--reference", action="store_true", help="only the reference server's checks")
+    sp.add_argument("--combined", action="store_true",
+                    help="one random combination and one final exponentiation for the round's proofs")
+    sp.add_argument("--aggregate", action="store_true",
+                    help="then aggregate each group over its accepted clients (aggregate-round's lines)")
     args = ap.parse_args(argv)
     fn = {"compile": cmd_compile, "info": cmd_info, "setup": cmd_setup,
           "r1cs-info": cmd_r1cs_info, "setup-r1cs": cmd_setup_r1cs, "export-vk": cmd_export_vk,
           "wtns": cmd_wtns, "prove": cmd_prove, "verify": cmd_verify, "verify-round": cmd_verify_round,
-          "aggregate-round": cmd_aggregate_round}[args.cmd]
+          "aggregate-round": cmd_aggregate_round, "admit-round": cmd_admit_round}[args.cmd]
     try:
         return fn(args) or 0
     except native.ZkflError as e:

@@ -104,6 +104,36 @@ class GroupRowsInfo(C.Structure):
                 ("last_dirty", C.c_uint32), ("last_plain", C.c_uint32), ("rows_build_ms", C.c_double)]
 
 
+class AdmitPhase(C.Structure):
+    """zkfl_admit_phase"""
+    _fields_ = [("present", _P), ("claimed", _P), ("signals", _P), ("proofs", _P)]
+
+
+class AdmitRound(C.Structure):
+    """zkfl_admit_round"""
+    _fields_ = [("n", C.c_size_t), ("dim", C.c_uint32), ("ids", _P), ("round", _P), ("tau_squared", _P),
+                ("vkeys", _P * 3), ("balance", AdmitPhase), ("training", AdmitPhase), ("secagg", AdmitPhase),
+                ("gradients", _P), ("masked_update", _P), ("weights", _P), ("peer_ptr", _P), ("peer_ids", _P)]
+
+
+# ZKFL_ADMIT_*: a client's code per phase (0 = accepted, else the first failing check) and the flags
+ADMIT_CODES = {
+    0: "OK",
+    1: "B_MISSING", 2: "B_SIG_ROOT_D", 3: "B_PROOF",
+    16: "T_MISSING", 17: "T_NO_BALANCE", 18: "T_BIND_ROOT_D", 19: "T_SIG_ROOT_D", 20: "T_SIG_ROOT_G",
+    21: "T_SIG_ROOT_W", 22: "T_SIG_ROUND", 23: "T_ROUND_STALE", 24: "T_SIG_TAU", 25: "T_ROOT_G_GRADIENT",
+    26: "T_ROOT_W_MODEL", 27: "T_PROOF",
+    32: "S_MISSING", 33: "S_NO_TRAINING", 34: "S_BIND_ROOT_G", 35: "S_BIND_ROOT_D", 36: "S_BIND_ROOT_W",
+    37: "S_SIG_CLIENT_ID", 38: "S_SIG_ROUND", 39: "S_ROUND_STALE", 40: "S_SIG_ROOT_D", 41: "S_SIG_ROOT_G",
+    42: "S_SIG_ROOT_W", 43: "S_SIG_ROOT_K", 44: "S_SIG_TAU", 45: "S_SIG_MASKED", 46: "S_SIG_PEERS", 47: "S_PROOF",
+}
+ADMIT_CHECK_ROUND, ADMIT_CHECK_MODEL, ADMIT_CHECK_PEERS, ADMIT_COMBINED = 1, 2, 4, 8
+ADMIT_PHASES = ("balance", "training", "secagg")
+ADMIT_FIELDS = {"balance": ("root_D",), "training": ("root_D", "root_G", "root_W", "round"),
+                "secagg": ("root_D", "root_G", "root_W", "root_K", "round")}   # the claimed fields, in order
+ADMIT_NPUBLIC = {"balance": 5, "training": 6, "secagg": 7}                      # secagg: 7 + dim + peers
+
+
 # every exported symbol of include/zkfl.h with (restype, argtypes)
 SIGNATURES = {
     "zkfl_version": (C.c_int, []),
@@ -225,6 +255,8 @@ SIGNATURES = {
     "zkfl_secagg_mask": (C.c_int, [_P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.c_uint32]),
     "zkfl_secagg_aggregate": (C.c_int, [_P, C.c_size_t, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                         C.c_uint32]),
+    "zkfl_round_admit": (C.c_int, [_P, C.POINTER(AdmitRound), C.c_uint32, _P, _P]),
+    "zkfl_debug_admit_static": (C.c_int, [_P, C.POINTER(AdmitRound), C.c_uint32, C.c_uint32, _P]),
 }
 
 
@@ -763,6 +795,76 @@ class Context(_Handle):
                                           _addr(signed) if decode else None, _addr(oor) if decode else None,
                                           chunk_terms))
         return sums, signed, (oor.astype(bool) if decode else None)
+
+    # admitting a round (csrc/admit.hip; zkfl/admit.py holds the package-level interface)
+    @staticmethod
+    def _admit_round(r: dict, flags: int, s_npub: int, proofs: bool):
+        """The arrays of a round -> (zkfl_admit_round, what must stay alive during the call).  r: "ids"
+        (n), "round", "tau_squared" (integers < r), "dim", "gradients" (int64 n x dim), "masked_update"
+        (uint8 n x dim x 32), per phase r[phase] = {"present" (n bytes), "claimed" (uint8 n x fields x 32),
+        "signals" (uint8 n x nPublic x 32), "proofs" (uint8 n x 256)}, optional "weights" (dim x 32),
+        "peer_ptr" (n + 1) and "peer_ids"."""
+        import numpy as np
+        ids = _u64(r["ids"])
+        n, dim = ids.size, int(r["dim"])
+        keep = [ids, int(r["round"]).to_bytes(32, "little"), int(r["tau_squared"]).to_bytes(32, "little")]
+        a = AdmitRound()
+        a.n, a.dim, a.ids = n, dim, _addr(ids)
+        a.round = C.cast(C.c_char_p(keep[1]), _P)
+        a.tau_squared = C.cast(C.c_char_p(keep[2]), _P)
+
+        def arr(x, size, what, dtype=np.uint8):
+            if x is None:
+                return None
+            x = _u8(x) if dtype is np.uint8 else np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+            if x.size != size:
+                raise ZkflError(-1, f"admit: {what} holds {x.size} entries, expected {size}")
+            keep.append(x)
+            return _addr(x)
+
+        for name in ADMIT_PHASES:
+            ph, src = getattr(a, name), r[name]
+            npub = ADMIT_NPUBLIC[name] if name != "secagg" else s_npub
+            ph.present = arr(src.get("present"), n, f"{name} present")
+            ph.claimed = arr(src.get("claimed"), 32 * n * len(ADMIT_FIELDS[name]), f"{name} claimed")
+            ph.signals = arr(src.get("signals"), 32 * n * npub, f"{name} signals")
+            ph.proofs = arr(src.get("proofs"), 256 * n, f"{name} proofs") if proofs else None
+        a.gradients = arr(r.get("gradients"), n * dim, "gradients", np.int64)
+        a.masked_update = arr(r.get("masked_update"), 32 * n * dim, "masked_update")
+        a.weights = arr(r.get("weights"), 32 * dim, "weights")
+        if r.get("peer_ptr") is not None:
+            ptr = _u64(r["peer_ptr"])
+            if ptr.size != n + 1:
+                raise ZkflError(-1, f"admit: peer_ptr holds {ptr.size} entries for {n} clients")
+            pid = _u64(r.get("peer_ids", ()))
+            if int(ptr[n]) < 1 << 32 and ptr[0] == 0 and pid.size != int(ptr[n]):
+                raise ZkflError(-1, f"admit: peer_ptr counts {int(ptr[n])} peers, peer_ids holds {pid.size}")
+            keep += [ptr, pid]
+            a.peer_ptr, a.peer_ids = ptr.ctypes.data, _addr(pid)
+        return a, keep
+
+    def round_admit(self, r: dict, vkeys, flags: int = 7):
+        """zkfl_round_admit: r as _admit_round describes, vkeys the three VerifyingKey (balance, training,
+        secagg) -> (codes: uint32 array (3, n), phase-major; the verifier's report dict).  flags: ADMIT_*;
+        the default turns the three added checks on."""
+        import numpy as np
+        a, keep = self._admit_round(r, flags, vkeys[2].n_public, True)
+        for i, k in enumerate(vkeys):
+            a.vkeys[i] = k.h
+        codes = np.zeros((3, a.n), np.uint32)
+        rep = (C.c_uint32 * len(ROUND_REPORT_FIELDS))()
+        check(lib().zkfl_round_admit(self.h, C.byref(a), flags, _addr(codes), C.cast(rep, _P)))
+        del keep
+        return codes, dict(zip(ROUND_REPORT_FIELDS, (int(v) for v in rep)))
+
+    def debug_admit_static(self, r: dict, secagg_npublic: int, flags: int = 7):
+        """zkfl_debug_admit_static: the static codes alone (no keys, no proofs) -> uint32 array (3, n)."""
+        import numpy as np
+        a, keep = self._admit_round(r, flags, secagg_npublic, False)
+        codes = np.zeros((3, a.n), np.uint32)
+        check(lib().zkfl_debug_admit_static(self.h, C.byref(a), flags, secagg_npublic, _addr(codes)))
+        del keep
+        return codes
 
     # multi-key batches (one federated round: several circuits' proofs interleaved on one device)
     def prove_multi(self, jobs, rs: bytes | None = None) -> list:
