@@ -856,6 +856,68 @@ int zkfl_round_admit(zkfl_ctx* ctx, const zkfl_admit_round* in, uint32_t flags, 
 int zkfl_debug_admit_static(zkfl_ctx* ctx, const zkfl_admit_round* in, uint32_t flags, uint32_t secagg_npublic,
                             uint32_t* codes);
 
+/* Preparing a round: what the reference's clients compute before they prove, for all clients of a
+ * round in one call (csrc/prepare.hip) -- the round loop of tests/full_system_simulation.mjs:1278-1343:
+ * the dataset tree and its Merkle openings (computeDatasetCommitment :308-335, getMerkleProof :225-238),
+ * the fixed-point gradient with its floor division (_computeVerifiedGradient :511-553), gradPos /
+ * gradNeg and the clipping test (:411-431), the commitments root_W, root_G, root_K and the masked
+ * update (:433-438, :565-609).  The results are the flat input vectors of balance_unified(samples,
+ * depth, dim), sgd_verified(batch, dim, depth, precision) and secure_masked_update(dim, peers) in
+ * declaration order, 32 B std form -- what zkfl_witness_compute / zkfl_groth16_full_prove_batch take --
+ * and the fields a client puts into its packages (zkfl_admit_round reads them back).
+ *
+ * Semantics, the reference's: leaf i = vectorHash(features[i] || label[i]); the tree is padded with
+ * Poseidon([0]); pathIndices[l] = (idx >> l) & 1; summed[j] = sum over the batch rows i of
+ * (<f_i, w> - label_i * precision) * f_ij; gradient = floor(summed / (batch * precision)); remainder =
+ * summed - gradient * (batch * precision), in [0, batch * precision); root_W = vectorHash(weights);
+ * root_G = Poseidon(vectorHash(g), Poseidon(id, round)) over the signed gradient; root_K =
+ * Poseidon(master, keys...); masked as zkfl_secagg_mask.  The secagg vector carries the training
+ * part's root_D, root_G, root_W and gradient.  Key agreement stays the caller's protocol. */
+#define ZKFL_PREPARE_OK 0
+#define ZKFL_PREPARE_NORM 1 /* sum g^2 > tau_squared: the reference throws (:428-431); the inputs are still
+                               written and the witness engine refuses them */
+#define ZKFL_PREPARE_MAX_DIM 255  /* a leaf has dim + 1 <= 256 values */
+#define ZKFL_PREPARE_MAX_PEERS 15 /* root_K is one Poseidon of peers + 1 inputs */
+typedef struct {
+  size_t n;              /* clients */
+  const uint64_t* ids;   /* n client ids */
+  uint32_t samples;      /* 1..2^depth samples per client */
+  uint32_t dim;          /* 1..ZKFL_PREPARE_MAX_DIM */
+  uint32_t depth;        /* 1..ZKFL_MERKLE_MAX_DEPTH */
+  uint32_t batch;        /* 1..samples */
+  uint32_t precision;    /* > 0 */
+  uint32_t peers;        /* 0..ZKFL_PREPARE_MAX_PEERS; 0: no secagg part */
+  const int64_t* features;  /* n x samples x dim, signed: a negative x stands for r - |x| */
+  const uint8_t* labels;    /* n x samples, 0 or 1 */
+  const uint32_t* batch_idx; /* n x batch sample indices, or NULL for 0..batch-1 (the reference's choice) */
+  const int64_t* weights;   /* dim: the global model, signed */
+  const uint8_t* round;     /* 32 B */
+  uint64_t tau_squared;     /* < 2^64 - 1: the circuit's LessThan(64) takes tau + 1 */
+  const uint64_t* peer_ids; /* n x peers */
+  const uint8_t* keys;      /* n x peers x 32 B, aligned with peer_ids */
+  const uint8_t* master_keys; /* n x 32 B */
+} zkfl_prepare_round;
+/* Every pointer nullable: NULL means that part is neither assembled nor copied back. */
+typedef struct {
+  uint8_t* balance_inputs;  /* n x (5 + samples*dim + samples + 2*samples*depth) x 32 B */
+  uint8_t* training_inputs; /* n x (6 + 5*dim + batch*dim + batch + 2*batch*depth) x 32 B */
+  uint8_t* secagg_inputs;   /* n x (8 + 2*dim + 2*peers) x 32 B */
+  uint8_t* roots;           /* n x 4 x 32 B: root_D, root_G, root_W, root_K (root_K zero when peers == 0) */
+  int64_t* gradients;       /* n x dim */
+  uint8_t* masked;          /* n x dim x 32 B */
+  uint32_t* c1;             /* n: the number of labels that are 1 */
+  uint32_t* status;         /* n: ZKFL_PREPARE_* */
+} zkfl_prepare_out;
+/* The norm is accumulated saturating, so it cannot wrap.  With the overflow bound below in force the
+ * device works in plain int64.
+ * Errors, all ZKFL_E_ARG before any device work, the message naming the client or index: dim, depth,
+ * samples, batch or peers outside the ranges above; a batch_idx >= samples; a label not 0 or 1;
+ * precision 0; tau_squared = 2^64 - 1; peers == 0 with secagg_inputs, masked, peer_ids, keys or
+ * master_keys non-NULL; a peer equal to its client's id, or repeated in a client's list; a key,
+ * master key or round >= r; and, with F = max |feature| and W = max |weight|,
+ * batch * F * (dim * F * W + precision) > 2^63 - 1.  n == 0 is valid and does nothing. */
+int zkfl_round_prepare(zkfl_ctx* ctx, const zkfl_prepare_round* in, const zkfl_prepare_out* out);
+
 /* Dev-ceremony fixed-base multiplications: out[i] = scalars[i] * generator, mont affine. */
 int zkfl_setup_g1_gen_mul(zkfl_ctx* ctx, const uint8_t* scalars, size_t n, uint8_t* out);
 int zkfl_setup_g2_gen_mul(zkfl_ctx* ctx, const uint8_t* scalars, size_t n, uint8_t* out);

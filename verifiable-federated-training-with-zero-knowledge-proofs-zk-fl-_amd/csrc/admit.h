@@ -40,4 +40,26 @@ struct AdmitJob {
 // codes.  Synchronises st.
 int admit_static_run(const PosTables* P, const AdmitJob& J, hipStream_t st, Profiler* prof, std::string& err);
 
+
+// the reference's gradient map (:955), standard form: g >= 0 -> g, g < 0 -> r - |g|, with |g| taken
+// in unsigned arithmetic (INT64_MIN has no int64 negation)
+ZK_DEV Fr fr_from_i64(int64_t g) {
+  const uint64_t u = (uint64_t)g;
+  const bool neg = g < 0;
+  Fr v = fp_zero<FrP>();
+  const uint64_t mag = neg ? 0ull - u : u;
+  v.v[0] = (uint32_t)mag;
+  v.v[1] = (uint32_t)(mag >> 32);
+  return neg ? fp_neg(v) : v;  // |g| > 0 here, so r - |g| is in 1..r-1
+}
+
+// The device code of the gradient commitment on device buffers, shared with csrc/prepare.hip.
+// out[i] = the reference's gradient map of grad[i] (g >= 0 -> g, g < 0 -> r - |g|), standard form.
+hipError_t admit_signed_dev(const int64_t* grad, size_t count, Fr* out, hipStream_t st);
+// The chunk pass of a vector hash of len in 17..256 values: rows [n_rows x len] standard form ->
+// chunk [n_rows x ceil(len / 16)] Montgomery chunk hashes; all full chunks of all rows in one launch,
+// the short last chunk in one launch of the width it has.  The top hash is poseidon_rows over chunk.
+hipError_t admit_chunks_dev(const PosTables* P, const Fr* rows, size_t n_rows, uint32_t len, Fr* chunk,
+                            hipStream_t st);
+
 }  // namespace zkfl

@@ -80,18 +80,6 @@ ZK_DEV bool fr_is_u64(const Fr& a, uint64_t x) {
   return d == 0;
 }
 
-// the reference's gradient map (:955), standard form: g >= 0 -> g, g < 0 -> r - |g|, with |g| taken
-// in unsigned arithmetic (INT64_MIN has no int64 negation)
-ZK_DEV Fr fr_from_i64(int64_t g) {
-  const uint64_t u = (uint64_t)g;
-  const bool neg = g < 0;
-  Fr v = fp_zero<FrP>();
-  const uint64_t mag = neg ? 0ull - u : u;
-  v.v[0] = (uint32_t)mag;
-  v.v[1] = (uint32_t)(mag >> 32);
-  return neg ? fp_neg(v) : v;  // |g| > 0 here, so r - |g| is in 1..r-1
-}
-
 // dim > 16: the gradients as standard-form field elements, the input of the chunk pass
 __global__ __launch_bounds__(256) void k_admit_signed(const int64_t* __restrict__ grad, size_t count,
                                                       Fr* __restrict__ out) {
@@ -249,6 +237,27 @@ hipError_t clients_of_width(uint32_t t, const PosTables* P, const AdmitDev& D, h
 
 }  // namespace
 
+hipError_t admit_signed_dev(const int64_t* grad, size_t count, Fr* out, hipStream_t st) {
+  if (!count) return hipSuccess;
+  hipLaunchKernelGGL(k_admit_signed, dim3(zk_grid(count, 256)), dim3(256), 0, st, grad, count, out);
+  return hipGetLastError();
+}
+
+hipError_t admit_chunks_dev(const PosTables* P, const Fr* rows, size_t n_rows, uint32_t len, Fr* chunk,
+                            hipStream_t st) {
+  if (len <= VHASH_CHUNK || len > VHASH_CHUNK * VHASH_CHUNK) return hipErrorInvalidValue;
+  if (!n_rows) return hipSuccess;
+  const uint32_t nch = (len + VHASH_CHUNK - 1) / VHASH_CHUNK, full = len / VHASH_CHUNK, tail = len % VHASH_CHUNK;
+  PosConsts K17;
+  pos_tables_width(P, VHASH_CHUNK + 1, &K17.C, &K17.M, &K17.rp);
+  hipLaunchKernelGGL(k_admit_chunks, dim3(zk_grid(n_rows * full, 256)), dim3(256), 0, st, K17, rows, n_rows, len, nch,
+                     full, chunk);
+  ZK_CHECK(hipGetLastError());
+  if (tail)  // the short last chunk of every row: one launch of the width it has
+    ZK_CHECK(poseidon_rows(P, tail, n_rows, rows + (size_t)full * VHASH_CHUNK, len, false, chunk + full, nch, true, st));
+  return hipSuccess;
+}
+
 int admit_static_run(const PosTables* P, const AdmitJob& J, hipStream_t st, Profiler* prof, std::string& err) {
   const char* const where = "admit";
   const size_t n = J.n;
@@ -312,18 +321,8 @@ int admit_static_run(const PosTables* P, const AdmitJob& J, hipStream_t st, Prof
 
   if (nch) {
     const int pc = prof ? prof->begin("admit_chunks", st) : -1;
-    hipLaunchKernelGGL(k_admit_signed, dim3(zk_grid(n * dim, 256)), dim3(256), 0, st, d_grad, n * dim, d_gfr);
-    HIP_TRY_ERR(hipGetLastError(), where, err);
-    const uint32_t full = dim / VHASH_CHUNK, tail = dim % VHASH_CHUNK;
-    PosConsts K17;
-    pos_tables_width(P, VHASH_CHUNK + 1, &K17.C, &K17.M, &K17.rp);
-    hipLaunchKernelGGL(k_admit_chunks, dim3(zk_grid(n_rows * full, 256)), dim3(256), 0, st, K17, d_gfr, n_rows, dim,
-                       nch, full, d_chunk);
-    HIP_TRY_ERR(hipGetLastError(), where, err);
-    if (tail)  // the short last chunk of every row: one launch of the width it has
-      HIP_TRY_ERR(poseidon_rows(P, tail, n_rows, d_gfr + (size_t)full * VHASH_CHUNK, dim, false, d_chunk + full, nch,
-                                true, st),
-                  where, err);
+    HIP_TRY_ERR(admit_signed_dev(d_grad, n * dim, d_gfr, st), where, err);
+    HIP_TRY_ERR(admit_chunks_dev(P, d_gfr, n_rows, dim, d_chunk, st), where, err);
     if (prof) prof->end(pc, st, (double)n_rows * nch);  // units: chunk hashes
   }
   D.n = n;

@@ -27,6 +27,9 @@ void pos_tables_free(PosTables* p);
 // The tables of one width t in 2..17 (device pointers, Montgomery): C[(8 + rp) * t], M[t][t].
 // For the units that run poseidon_perm0 in kernels of their own (csrc/secagg.hip).
 void pos_tables_width(const PosTables* p, uint32_t t, const Fr** C, const Fr** M, uint32_t* rp);
+// The zero-subtree hashes z_0 = Poseidon([0]), z_{l+1} = Poseidon([z_l, z_l]) for l <= 32 (device,
+// Montgomery), for the units that walk trees in kernels of their own (csrc/prepare.hip).
+const Fr* pos_tables_zeros(const PosTables* p);
 
 // out[i] = in[i] in Montgomery form (device, n elements)
 hipError_t fr_to_mont_batch(const Fr* in, size_t n, Fr* out, hipStream_t st);

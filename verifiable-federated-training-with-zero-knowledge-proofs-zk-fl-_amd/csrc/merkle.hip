@@ -310,6 +310,8 @@ void pos_tables_width(const PosTables* p, uint32_t t, const Fr** C, const Fr** M
   *rp = p->w[t].rp;
 }
 
+const Fr* pos_tables_zeros(const PosTables* p) { return p->zeros; }
+
 int pos_tables_create(PosTables** out, hipStream_t st, std::string& err) {
   // host: raw constants of every width; device: Montgomery form, MDS inverses, zero hashes
   size_t total = 0, off[18] = {}, nc[18] = {};

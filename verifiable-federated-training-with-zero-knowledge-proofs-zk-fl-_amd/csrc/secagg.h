@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 #include "field.h"
 #include "prof.h"
@@ -49,5 +50,31 @@ uint32_t secagg_default_chunk(uint64_t terms, uint32_t dim);
 
 // Arguments are the caller's to validate (csrc/secagg.hip's entry points do).  Synchronises st.
 int secagg_run(const PosTables* P, const SecaggJob& J, hipStream_t st, Profiler* prof, std::string& err);
+
+
+// The same evaluation on device buffers, for a unit that has its operands on the device already
+// (csrc/prepare.hip): launches only, no copies and no synchronisation.  raw holds the n_terms keys
+// and then the round, standard form; key, lo, hi, neg and part are scratch of n_terms + 1, n_terms,
+// n_terms, n_terms and n_chunks x dim elements; the chunk arrays are secagg_chunk_layout's, uploaded.
+struct SecaggDev {
+  size_t n_rows = 0, n_terms = 0, n_chunks = 0;
+  uint32_t dim = 0, chunk_terms = 1;
+  bool negate_if_less = false;
+  const Fr* raw = nullptr;
+  const uint64_t *term_a = nullptr, *term_b = nullptr, *term_ptr = nullptr, *chunk_ptr = nullptr;
+  const uint32_t* chunk_row = nullptr;
+  const uint64_t* base_ptr = nullptr;  // or null, as SecaggJob's
+  const Fr* base = nullptr;
+  Fr *key = nullptr, *lo = nullptr, *hi = nullptr;
+  uint8_t* neg = nullptr;
+  Fr* part = nullptr;
+  Fr* out = nullptr;
+  int64_t* signed_out = nullptr;
+  uint8_t* range_out = nullptr;
+};
+// a row's terms in chunks of ct: chunk_ptr[row] = its first chunk, chunk_row[c] = the chunk's row
+void secagg_chunk_layout(const uint64_t* term_ptr, size_t n, uint32_t ct, std::vector<uint64_t>& chunk_ptr,
+                         std::vector<uint32_t>& chunk_row);
+int secagg_eval_dev(const PosTables* P, const SecaggDev& S, hipStream_t st, Profiler* prof, std::string& err);
 
 }  // namespace zkfl

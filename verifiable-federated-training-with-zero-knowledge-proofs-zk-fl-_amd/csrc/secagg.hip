@@ -163,18 +163,54 @@ uint32_t secagg_default_chunk(uint64_t terms, uint32_t dim) {
   return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c, 1), SECAGG_MAX_CHUNK);
 }
 
+void secagg_chunk_layout(const uint64_t* term_ptr, size_t n, uint32_t ct, std::vector<uint64_t>& chunk_ptr,
+                         std::vector<uint32_t>& chunk_row) {
+  chunk_ptr.assign(n + 1, 0);
+  for (size_t r = 0; r < n; r++) chunk_ptr[r + 1] = chunk_ptr[r] + (term_ptr[r + 1] - term_ptr[r] + ct - 1) / ct;
+  chunk_row.resize((size_t)chunk_ptr[n]);  // <= T < 2^32
+  for (size_t r = 0; r < n; r++)
+    for (uint64_t c = chunk_ptr[r]; c < chunk_ptr[r + 1]; c++) chunk_row[c] = (uint32_t)r;
+}
+
+int secagg_eval_dev(const PosTables* P, const SecaggDev& S, hipStream_t st, Profiler* prof, std::string& err) {
+  const char* const where = "secagg";
+  const size_t cells = S.n_rows * S.dim, lanes = S.n_chunks * S.dim;
+  if ((cells + 255) / 256 > MAX_GRID || (lanes + 255) / 256 > MAX_GRID) {
+    err = "secagg: rows x dim exceeds one launch";
+    return ZKFL_E_ARG;
+  }
+  if (lanes) {
+    PosConsts K;
+    pos_tables_width(P, 6, &K.C, &K.M, &K.rp);
+    HIP_TRY_ERR(fr_to_mont_batch(S.raw, S.n_terms + 1, S.key, st), where, err);  // the keys and the round, once per call
+    hipLaunchKernelGGL(k_secagg_prepare, dim3(zk_grid(S.n_terms, 256)), dim3(256), 0, st, S.term_a, S.term_b, S.n_terms,
+                       (uint32_t)S.negate_if_less, S.lo, S.hi, S.neg);
+    HIP_TRY_ERR(hipGetLastError(), where, err);
+    const SecaggTerms tm = {S.key, S.lo, S.hi, S.neg};
+    const int pi = prof ? prof->begin("secagg_terms", st) : -1;
+    hipLaunchKernelGGL(k_secagg_terms, dim3(zk_grid(lanes, 256)), dim3(256), 0, st, K, tm, S.n_terms, S.term_ptr,
+                       S.chunk_ptr, S.chunk_row, S.n_chunks, S.dim, S.chunk_terms, S.part);
+    HIP_TRY_ERR(hipGetLastError(), where, err);
+    if (prof) prof->end(pi, st, (double)S.n_terms * S.dim);  // units: hashes
+  }
+  const int pf = prof ? prof->begin("secagg_fold", st) : -1;
+  hipLaunchKernelGGL(k_secagg_fold, dim3(zk_grid(cells, 256)), dim3(256), 0, st, S.n_rows, S.dim, S.chunk_ptr, S.part,
+                     S.base_ptr, S.base, S.out, S.signed_out, S.range_out);
+  HIP_TRY_ERR(hipGetLastError(), where, err);
+  if (prof) prof->end(pf, st, (double)cells);
+  return ZKFL_OK;
+}
+
 int secagg_run(const PosTables* P, const SecaggJob& J, hipStream_t st, Profiler* prof, std::string& err) {
   const char* const where = "secagg";
   const size_t n = J.n_rows, T = (size_t)J.term_ptr[n];
   const uint32_t dim = J.dim;
   const uint32_t ct = J.chunk_terms ? J.chunk_terms : secagg_default_chunk(T, dim);
   // a row's terms in chunks of ct: chunk_ptr[row] = its first chunk, chunk_row[c] = the chunk's row
-  std::vector<uint64_t> chunk_ptr(n + 1, 0);
-  for (size_t r = 0; r < n; r++) chunk_ptr[r + 1] = chunk_ptr[r] + (J.term_ptr[r + 1] - J.term_ptr[r] + ct - 1) / ct;
-  const size_t n_chunks = (size_t)chunk_ptr[n];  // <= T < 2^32
-  std::vector<uint32_t> chunk_row(n_chunks);
-  for (size_t r = 0; r < n; r++)
-    for (uint64_t c = chunk_ptr[r]; c < chunk_ptr[r + 1]; c++) chunk_row[c] = (uint32_t)r;
+  std::vector<uint64_t> chunk_ptr;
+  std::vector<uint32_t> chunk_row;
+  secagg_chunk_layout(J.term_ptr, n, ct, chunk_ptr, chunk_row);
+  const size_t n_chunks = chunk_row.size();
   const size_t cells = n * dim, lanes = n_chunks * dim;
   if ((cells + 255) / 256 > MAX_GRID || (lanes + 255) / 256 > MAX_GRID) {
     err = "secagg: rows x dim exceeds one launch";
@@ -218,25 +254,30 @@ int secagg_run(const PosTables* P, const SecaggJob& J, hipStream_t st, Profiler*
   if (J.n_base)
     HIP_TRY_ERR(hipMemcpyAsync(d_base, J.base, J.n_base * dim * 32, hipMemcpyHostToDevice, st), where, err);
 
-  if (lanes) {
-    PosConsts K;
-    pos_tables_width(P, 6, &K.C, &K.M, &K.rp);
-    HIP_TRY_ERR(fr_to_mont_batch(d_raw, T + 1, d_key, st), where, err);  // the keys and the round, once per call
-    hipLaunchKernelGGL(k_secagg_prepare, dim3(zk_grid(T, 256)), dim3(256), 0, st, d_a, d_b, T,
-                       (uint32_t)J.negate_if_less, d_lo, d_hi, d_neg);
-    HIP_TRY_ERR(hipGetLastError(), where, err);
-    const SecaggTerms tm = {d_key, d_lo, d_hi, d_neg};
-    const int pi = prof ? prof->begin("secagg_terms", st) : -1;
-    hipLaunchKernelGGL(k_secagg_terms, dim3(zk_grid(lanes, 256)), dim3(256), 0, st, K, tm, T, d_tptr, d_cptr, d_crow,
-                       n_chunks, dim, ct, d_part);
-    HIP_TRY_ERR(hipGetLastError(), where, err);
-    if (prof) prof->end(pi, st, (double)T * dim);  // units: hashes
-  }
-  const int pf = prof ? prof->begin("secagg_fold", st) : -1;
-  hipLaunchKernelGGL(k_secagg_fold, dim3(zk_grid(cells, 256)), dim3(256), 0, st, n, dim, d_cptr, d_part, d_bptr,
-                     d_base, d_out, d_signed, d_range);
-  HIP_TRY_ERR(hipGetLastError(), where, err);
-  if (prof) prof->end(pf, st, (double)cells);
+  SecaggDev S;
+  S.n_rows = n;
+  S.n_terms = T;
+  S.n_chunks = n_chunks;
+  S.dim = dim;
+  S.chunk_terms = ct;
+  S.negate_if_less = J.negate_if_less;
+  S.raw = d_raw;
+  S.term_a = d_a;
+  S.term_b = d_b;
+  S.term_ptr = d_tptr;
+  S.chunk_ptr = d_cptr;
+  S.chunk_row = d_crow;
+  S.base_ptr = d_bptr;
+  S.base = d_base;
+  S.key = d_key;
+  S.lo = d_lo;
+  S.hi = d_hi;
+  S.neg = d_neg;
+  S.part = d_part;
+  S.out = d_out;
+  S.signed_out = d_signed;
+  S.range_out = d_range;
+  if (int rc = secagg_eval_dev(P, S, st, prof, err)) return rc;
   HIP_TRY_ERR(hipMemcpyAsync(J.out, d_out, cells * 32, hipMemcpyDeviceToHost, st), where, err);
   if (J.signed_out) {
     HIP_TRY_ERR(hipMemcpyAsync(J.signed_out, d_signed, cells * 8, hipMemcpyDeviceToHost, st), where, err);

@@ -67,6 +67,19 @@
         --aggregate: then close each group over the clients whose secagg code is 0 (their masked updates
         are signals 7..7+dim of their public.json) with the group's "revealed" keys, and print
         aggregate-round's lines; a group without an accepted client prints "sum": null
+    python -m zkfl prepare-round <manifest.json> -o DIR      the clients' half of a round (:1278-1343) in one call
+        (zkfl/prepare.py): dataset trees and Merkle openings, fixed-point gradients, commitments and
+        masked updates.  manifest.json: {"round", "tau_squared", "depth", "batch", "precision", "weights":
+        [dim signed integers], "clients": [{"id", "features": [[dim integers] per sample], "labels": [0 or
+        1 per sample], "batch_idx": [batch sample indices] (optional), "peers": [ids], "keys": [one per
+        peer], "master_key"}]}; every client has the same shape, and "peers", "keys" and "master_key" may
+        be absent from all of them (no secagg part).  "harness_keys": true instead of keys takes the
+        harness's simulated keys (:1321-1336), every client's peers being the other clients.  Writes
+        client<ID>_{balance,training,secagg}_input.json, the harness's file names, and prepared.json
+        ({"clients": [{"id", "status", "root_D", "root_G", "root_W", "root_K", "gradient", "masked_update",
+        "c1"}]}) into DIR; exit 0 when every client is OK, 1 when some client's gradient is above the
+        clipping bound (status NORM; its files are still written and the witness engine refuses them),
+        2 on a manifest of another shape or a value the library refuses (decided before the GPU is touched)
 
 <circuit> is one of zkfl.circuits.CIRCUITS (poseidon_hash2, sgd_verified, sgd_step_v5,
 balance_unified, secure_masked_update) followed by its integer template parameters.  GPU
@@ -447,6 +460,70 @@ def cmd_admit_round(args):
     return rc
 
 
+def _prepare_manifest(path):
+    """manifest.json of `prepare-round` -> the packed spec of zkfl/prepare.py, or None with a message on
+    stderr.  Host only."""
+    from . import prepare
+
+    def bad(msg):
+        print(f"[ERROR] zkfl: {path}: {msg}", file=sys.stderr)
+
+    shape = ('expected {"round", "tau_squared", "depth", "batch", "precision", "weights", "clients": [{"id", '
+             '"features", "labels"}]} (python -m zkfl --help)')
+    try:
+        with open(path) as f:
+            man = json.load(f)
+    except (OSError, ValueError) as e:
+        return bad(e)
+    try:
+        if not isinstance(man, dict) or not isinstance(man["clients"], list) or not man["clients"]:
+            return bad(shape)
+        cl = man["clients"]
+        ids = [int(c["id"]) for c in cl]
+        feats = [c["features"] for c in cl]
+        spec = {"ids": ids, "samples": len(feats[0]), "dim": len(man["weights"]), "depth": man["depth"],
+                "batch": man["batch"], "precision": man["precision"], "weights": man["weights"],
+                "round": man["round"], "tau_squared": man["tau_squared"], "features": feats,
+                "labels": [c["labels"] for c in cl]}
+        if any(c.get("batch_idx") is not None for c in cl):
+            spec["batch_idx"] = [c["batch_idx"] for c in cl]
+        if man.get("harness_keys"):
+            spec["peers"], spec["keys"], spec["master_keys"] = prepare.harness_keys(ids)
+        elif any(c.get("peers") is not None for c in cl):
+            spec["peers"] = [c["peers"] for c in cl]
+            spec["keys"] = [c["keys"] for c in cl]
+            spec["master_keys"] = [c["master_key"] for c in cl]
+        return prepare.pack(spec)
+    except ValueError as e:
+        return bad(e)
+    except (KeyError, TypeError, AttributeError, IndexError):
+        return bad(shape)
+
+
+def cmd_prepare_round(args):
+    packed = _prepare_manifest(args.manifest)
+    if packed is None:
+        return 2
+    from . import prepare
+    with _ctx() as ctx:
+        res = prepare.prepare_round(ctx, None, packed=packed)
+    os.makedirs(args.out, exist_ok=True)
+    summary = []
+    for i, cid in enumerate(res.ids):
+        for phase in res.inputs:
+            with open(os.path.join(args.out, f"client{cid}_{phase}_input.json"), "w") as f:
+                json.dump(res.input_json(phase, i), f)
+        d, g, w, k = (str(x) for x in prepare._ints(res.roots[i]))
+        summary.append({"id": cid, "status": prepare.STATUS[int(res.status[i])], "root_D": d, "root_G": g, "root_W": w,
+                        "root_K": k if packed["peers"] else None, "gradient": [int(x) for x in res.gradients[i]],
+                        "masked_update": [str(x) for x in prepare._ints(res.masked[i])] if res.masked is not None else None,
+                        "c1": int(res.c1[i])})
+        print(f"client {cid}: {summary[-1]['status']}")
+    with open(os.path.join(args.out, "prepared.json"), "w") as f:
+        json.dump({"round": str(packed["round"]), "tau_squared": str(packed["tau_squared"]), "clients": summary}, f)
+    return 0 if res.ok else 1
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     if snarkjs_cli.routes(argv):   # snarkjs ceremony strings and `wtns check` (zkfl/snarkjs_cli.py)
@@ -502,11 +579,15 @@ def main(argv=None):
                     help="one random combination and one final exponentiation for the round's proofs")
     sp.add_argument("--aggregate", action="store_true",
                     help="then aggregate each group over its accepted clients (aggregate-round's lines)")
+    sp = sub.add_parser("prepare-round")
+    sp.add_argument("manifest")
+    sp.add_argument("-o", "--out", required=True, help="the directory the input.json files go to")
     args = ap.parse_args(argv)
     fn = {"compile": cmd_compile, "info": cmd_info, "setup": cmd_setup,
           "r1cs-info": cmd_r1cs_info, "setup-r1cs": cmd_setup_r1cs, "export-vk": cmd_export_vk,
           "wtns": cmd_wtns, "prove": cmd_prove, "verify": cmd_verify, "verify-round": cmd_verify_round,
-          "aggregate-round": cmd_aggregate_round, "admit-round": cmd_admit_round}[args.cmd]
+          "aggregate-round": cmd_aggregate_round, "admit-round": cmd_admit_round,
+          "prepare-round": cmd_prepare_round}[args.cmd]
     try:
         return fn(args) or 0
     except native.ZkflError as e:

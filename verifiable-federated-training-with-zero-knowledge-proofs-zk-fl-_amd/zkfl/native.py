@@ -116,6 +116,34 @@ class AdmitRound(C.Structure):
                 ("gradients", _P), ("masked_update", _P), ("weights", _P), ("peer_ptr", _P), ("peer_ids", _P)]
 
 
+class PrepareRound(C.Structure):
+    """zkfl_prepare_round"""
+    _fields_ = [("n", C.c_size_t), ("ids", _P), ("samples", C.c_uint32), ("dim", C.c_uint32), ("depth", C.c_uint32),
+                ("batch", C.c_uint32), ("precision", C.c_uint32), ("peers", C.c_uint32), ("features", _P),
+                ("labels", _P), ("batch_idx", _P), ("weights", _P), ("round", _P), ("tau_squared", C.c_uint64),
+                ("peer_ids", _P), ("keys", _P), ("master_keys", _P)]
+
+
+class PrepareOut(C.Structure):
+    """zkfl_prepare_out"""
+    _fields_ = [("balance_inputs", _P), ("training_inputs", _P), ("secagg_inputs", _P), ("roots", _P),
+                ("gradients", _P), ("masked", _P), ("c1", _P), ("status", _P)]
+
+
+PREPARE_OK, PREPARE_NORM = 0, 1                                                  # ZKFL_PREPARE_*
+PREPARE_MAX_DIM, PREPARE_MAX_PEERS, MERKLE_MAX_DEPTH = 255, 15, 30
+PREPARE_OUTPUTS = ("balance_inputs", "training_inputs", "secagg_inputs", "roots", "gradients", "masked", "c1",
+                   "status")
+
+
+def prepare_lengths(samples: int, dim: int, depth: int, batch: int, peers: int) -> dict:
+    """The input counts of balance_unified(samples, depth, dim), sgd_verified(batch, dim, depth, .) and
+    secure_masked_update(dim, peers)."""
+    return {"balance": 5 + samples * dim + samples + 2 * samples * depth,
+            "training": 6 + 5 * dim + batch * dim + batch + 2 * batch * depth,
+            "secagg": 8 + 2 * dim + 2 * peers}
+
+
 # ZKFL_ADMIT_*: a client's code per phase (0 = accepted, else the first failing check) and the flags
 ADMIT_CODES = {
     0: "OK",
@@ -257,6 +285,7 @@ SIGNATURES = {
                                         C.c_uint32]),
     "zkfl_round_admit": (C.c_int, [_P, C.POINTER(AdmitRound), C.c_uint32, _P, _P]),
     "zkfl_debug_admit_static": (C.c_int, [_P, C.POINTER(AdmitRound), C.c_uint32, C.c_uint32, _P]),
+    "zkfl_round_prepare": (C.c_int, [_P, C.POINTER(PrepareRound), C.POINTER(PrepareOut)]),
 }
 
 
@@ -865,6 +894,58 @@ class Context(_Handle):
         check(lib().zkfl_debug_admit_static(self.h, C.byref(a), flags, secagg_npublic, _addr(codes)))
         del keep
         return codes
+
+    # preparing a round (csrc/prepare.hip; zkfl/prepare.py holds the spec-level interface)
+    def round_prepare(self, r: dict, want=None) -> dict:
+        """zkfl_round_prepare.  r: "ids" (n), "samples", "dim", "depth", "batch", "precision", "peers",
+        "features" (int64 n x samples x dim), "labels" (uint8 n x samples), "batch_idx" (uint32 n x batch,
+        or None), "weights" (int64 dim), "round" (integer < r), "tau_squared", and with peers > 0
+        "peer_ids" (uint64 n x peers), "keys" (uint8 n x peers x 32), "master_keys" (uint8 n x 32).
+        want: the names of PREPARE_OUTPUTS to compute (None: all the shape has; the secagg outputs
+        only with peers > 0).  -> {name: array}: the input vectors as uint8 (n, n_inputs, 32), "roots"
+        uint8 (n, 4, 32) (D, G, W, K), "gradients" int64 (n, dim), "masked" uint8 (n, dim, 32), "c1" and
+        "status" uint32 (n)."""
+        import numpy as np
+        ids = _u64(r["ids"])
+        n = ids.size
+        S, dim, depth, batch, peers = (int(r[k]) for k in ("samples", "dim", "depth", "batch", "peers"))
+        keep = [ids, int(r["round"]).to_bytes(32, "little")]
+        a = PrepareRound()
+        a.n, a.ids = n, _addr(ids)
+        a.samples, a.dim, a.depth, a.batch, a.precision, a.peers = S, dim, depth, batch, int(r["precision"]), peers
+        a.round = C.cast(C.c_char_p(keep[1]), _P)
+        a.tau_squared = int(r["tau_squared"])
+
+        def arr(x, size, what, dtype):
+            if x is None:
+                return None
+            x = _u8(x) if dtype is np.uint8 else np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+            if x.size != size:
+                raise ZkflError(-1, f"round_prepare: {what} holds {x.size} entries, expected {size}")
+            keep.append(x)
+            return x.ctypes.data          # an empty array keeps its (non-null) address: n == 0 stays valid
+
+        a.features = arr(r["features"], n * S * dim, "features", np.int64)
+        a.labels = arr(r["labels"], n * S, "labels", np.uint8)
+        a.batch_idx = arr(r.get("batch_idx"), n * batch, "batch_idx", np.uint32)
+        a.weights = arr(r["weights"], dim, "weights", np.int64)
+        a.peer_ids = arr(r.get("peer_ids"), n * peers, "peer_ids", np.uint64)
+        a.keys = arr(r.get("keys"), 32 * n * peers, "keys", np.uint8)
+        a.master_keys = arr(r.get("master_keys"), 32 * n, "master_keys", np.uint8)
+        names = [k for k in PREPARE_OUTPUTS if peers or k not in ("secagg_inputs", "masked")] if want is None else list(want)
+        ln = prepare_lengths(S, dim, depth, batch, peers)
+        shapes = {"balance_inputs": ((n, ln["balance"], 32), np.uint8), "training_inputs": ((n, ln["training"], 32), np.uint8),
+                  "secagg_inputs": ((n, ln["secagg"], 32), np.uint8), "roots": ((n, 4, 32), np.uint8),
+                  "gradients": ((n, dim), np.int64), "masked": ((n, dim, 32), np.uint8), "c1": ((n,), np.uint32),
+                  "status": ((n,), np.uint32)}
+        res, o = {}, PrepareOut()
+        for k in names:
+            shape, dt = shapes[k]
+            res[k] = np.zeros(shape, dt)
+            setattr(o, k, res[k].ctypes.data)
+        check(lib().zkfl_round_prepare(self.h, C.byref(a), C.byref(o)))
+        del keep
+        return res
 
     # multi-key batches (one federated round: several circuits' proofs interleaved on one device)
     def prove_multi(self, jobs, rs: bytes | None = None) -> list:
