@@ -75,7 +75,8 @@ int zkfl_ctx_set_profiling(zkfl_ctx* ctx, int enabled);
  * slots), "r1cs_terms", "r1cs_verdict" (the witness check's two passes), "verify_wave_g2",
  * "verify_wave_inputs", "verify_wave_pair" (the wave verifier's three kernels; units: proofs),
  * "verify_round_screen", "verify_round_pair", "verify_round_reduce", "verify_round_final" (the
- * combined round check's stages; units: proofs),
+ * combined round check's stages; units: proofs), "verify_round_groups" (the narrow entry's group
+ * exponentiations; units: groups),
  * "keycheck_points", "keycheck_rows", "keycheck_msm", "keycheck_pairing" (the key check's stages),
  * "ptaucheck_points", "ptaucheck_scalars", "ptaucheck_msm", "ptaucheck_pairing" (the ptau check's
  * stages, one record per chunk pass; units: points),
@@ -657,7 +658,8 @@ int zkfl_groth16_verify_multi(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* v
  * verdicts.  If every combined proof is valid the combination is 1; if one is not it is 1 with
  * probability <= 2^-128 over the z_i, so the results equal verify_multi's up to that probability.
  * Cost of a bad proof: a single invalid proof that passes the screening costs the round the
- * combined pass plus the per-proof pass.  Narrowing the bad jobs down by bisection is not done.
+ * combined pass plus the per-proof pass.  zkfl_groth16_verify_round_narrow below narrows the bad
+ * jobs down to groups first and re-verifies only those.
  *
  * z NULL: each z_i is drawn uniformly from [0, 2^128) with the OS CSPRNG inside the call (as
  * rs == NULL for proofs).  A caller's z (n x 16 B little endian) is for tests and forfeits
@@ -680,6 +682,47 @@ int zkfl_groth16_verify_round(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* v
 int zkfl_debug_verify_round(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
                             const size_t* npubs, const uint8_t* proofs, const uint8_t* z, size_t chunk,
                             uint8_t gt_out[384], int32_t* screened_out);
+/* zkfl_groth16_verify_round with a failed round narrowed to its bad groups: the same jobs, z,
+ * screening, argument checks and errors, and the same 384 B for the round.  The jobs of a pass (at
+ * most 4096), in the order the call sorts them -- by key, stable --, are cut into groups of `group`
+ * consecutive jobs; groups never cross a pass border, and the last group of a pass may be short.
+ * With the round's z_i every group g has a value of its own,
+ *
+ *   V_g = FE( prod_{i in g} ML(z_i (-A_i), B_i) * prod_k ML(S_gk, beta_k) ML(X_gk, gamma_k) ML(C_gk, delta_k) )
+ *
+ * (S, X, C summed over the group's unscreened jobs of key k), the product of its jobs' check values
+ * raised to z_i; the round's value is the product of the V_g, formed without exponentiating any of
+ * them.  A group holding an invalid job has V_g = 1 with probability <= 2^-128; a group of screened
+ * jobs only has V_g = 1.
+ * Verdict: when the round's value is 1 every combined job gets result 1 and no group is
+ * exponentiated.  Otherwise all V_g are computed in one launch, one wavefront each; the combined
+ * jobs of groups with V_g = 1 get result 1, and those of the other groups are verified one by one
+ * as zkfl_groth16_verify_multi does under ZKFL_VERIFY_AUTO.  The results equal verify_multi's up
+ * to (failing groups) x 2^-128.
+ * group: jobs per group, 1 .. the pass size min(n, 4096) (above it: ZKFL_E_ARG).  0 is the
+ * production policy: groups of ZKFL_ROUND_GROUP, and a failed round is narrowed only when at least
+ * ZKFL_ROUND_NARROW_MIN jobs were combined; below that every combined job is re-verified as by
+ * zkfl_groth16_verify_round, and the report shows groups 0 and fallback = combined. */
+#define ZKFL_ROUND_GROUP 64
+#define ZKFL_ROUND_NARROW_MIN 4096
+typedef struct {
+  uint32_t keys, screened, combined, passed; /* as zkfl_round_report */
+  uint32_t groups;     /* groups formed (0: the call did not narrow, see group == 0) */
+  uint32_t bad_groups; /* groups whose value is not 1 (0 when passed) */
+  uint32_t fallback;   /* jobs re-verified one by one */
+} zkfl_narrow_report;
+int zkfl_groth16_verify_round_narrow(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys,
+                                     const uint8_t* const* pubs, const size_t* npubs, const uint8_t* proofs,
+                                     const uint8_t* z, uint32_t group, int32_t* results, zkfl_narrow_report* report);
+/* Parity hook: group_of[i] = job i's group, counted across passes, and every group's V_g, 384 B
+ * each in zkfl_pairing's layout (exponentiated whether the round passes or not); *n_groups = how
+ * many.  cap: the groups gt_groups has room for; too few gives ZKFL_E_ARG with the count needed in
+ * *n_groups, before any device work.  z is required.  chunk as in zkfl_debug_verify_round; group
+ * as above, 0 = ZKFL_ROUND_GROUP (at most the pass size). */
+int zkfl_debug_verify_round_groups(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
+                                   const size_t* npubs, const uint8_t* proofs, const uint8_t* z, size_t chunk,
+                                   uint32_t group, uint32_t* group_of, uint8_t* gt_groups, size_t cap,
+                                   uint32_t* n_groups, int32_t* screened_out);
 /* Parity hook: zkfl_pairing (final_exp != 0) / zkfl_debug_miller_loop (final_exp == 0) computed by
  * the wave path's tower, Miller loop and final exponentiation; same inputs, layout and errors. */
 int zkfl_debug_wave_pairing(zkfl_ctx* ctx, size_t n, const uint8_t* g1, const uint8_t* g2, int final_exp,

@@ -12,6 +12,9 @@ correctness gate in SURVEY.md §8 a9, not the metric).
                                          combined call (zkfl_groth16_verify_round) in the same process,
                                          the combined call's per-stage records, and one round with a
                                          single invalid proof (the fallback's cost)
+    bench_verify.py --narrow [--group G] [sizes..]   the --round setup; per (n, invalid proofs) the
+                                         combined call against zkfl_groth16_verify_round_narrow
+                                         (groups of G, default 64), alternating in the same process
 """
 import json
 import os
@@ -112,7 +115,74 @@ def round_(sizes, repeats=10):
     ctx.close()
 
 
+NARROW_RECORDS = ROUND_RECORDS + ("verify_round_groups", "verify_wave_g2", "verify_wave_inputs", "verify_wave_pair")
+
+
+def _plus_g(job):
+    """The job with pi_c + G: it passes the screening and fails its check."""
+    from oracle import bn254 as bn
+    vk, pub, proof = job
+    c = bn.add((int.from_bytes(proof[192:224], "little"), int.from_bytes(proof[224:256], "little")), bn.G1_GEN)
+    return vk, pub, proof[:192] + c[0].to_bytes(32, "little") + c[1].to_bytes(32, "little")
+
+
+def narrow(sizes, group=64, repeats=10):
+    """--narrow: --round's jobs with b invalid proofs (pi_c + G) in b distinct groups, b in 0, 1, 8
+    and one per group.  Per (n, b) the existing combined call and the narrow call (groups of
+    `group`) alternate in the same process, one warm-up call each whose verdicts are checked, then
+    `repeats` timed calls each: one JSON line per route, then the narrow report and both routes'
+    per-stage event times."""
+    import statistics
+    ctx = native.Context(0)
+    made = _two_keys(ctx)
+    bad = [_plus_g(j) for j in made]
+    for n in sizes:
+        n0 = (n + 1) // 2  # the call orders the jobs by key: position p holds job 2p, n0 + p job 2p + 1
+        firsts = [off + g for off in range(0, n, 4096) for g in range(0, min(4096, n - off), group)]
+        for b in dict.fromkeys((0, 1, 8, len(firsts))):
+            if b > len(firsts):
+                continue
+            jobs = [made[i % 2] for i in range(n)]
+            want = [True] * n
+            for k in range(b):
+                p = firsts[k * len(firsts) // b]
+                i = 2 * p if p < n0 else 2 * (p - n0) + 1
+                jobs[i], want[i] = bad[i % 2], False
+            routes = {"verify_round": lambda: ctx.verify_round(jobs),
+                      "verify_round_narrow": lambda: ctx.verify_round_narrow(jobs, None, group)}
+            reports, ts = {}, {r: [] for r in routes}
+            for r, call in routes.items():  # warm-up, and the verdicts
+                got, reports[r] = call()
+                assert got == want, (r, n, b)
+            for _ in range(repeats):
+                for r, call in routes.items():
+                    t0 = time.perf_counter()
+                    call()
+                    ts[r].append((time.perf_counter() - t0) * 1e3)
+            for r in routes:
+                print(json.dumps({"route": r, "n": n, "bad": b, "group": group,
+                                  "median_ms": round(statistics.median(ts[r]), 3), "min_ms": round(min(ts[r]), 3),
+                                  "max_ms": round(max(ts[r]), 3), "repeats": repeats, "report": reports[r],
+                                  "build": native.build_id()}), flush=True)
+            for r, call in routes.items():
+                ctx.set_profiling(True)
+                ctx.profile_reset()
+                call()
+                prof = {k: round(ctx.profile(k)[0], 3) for k in NARROW_RECORDS}
+                ctx.set_profiling(False)
+                print(json.dumps({"profile_ms": prof, "route": r, "n": n, "bad": b}), flush=True)
+    ctx.close()
+
+
 def main():
+    if "--narrow" in sys.argv[1:]:
+        args = [x for x in sys.argv[1:] if x != "--narrow"]
+        group = 64
+        if "--group" in args:
+            at = args.index("--group")
+            group = int(args[at + 1])
+            del args[at:at + 2]
+        return narrow([int(x) for x in args] or [256, 1024, 4096, 8192], group)
     if "--round" in sys.argv[1:]:
         return round_([int(x) for x in sys.argv[1:] if x != "--round"] or [16, 256, 1024, 4096])
     if "--multi" in sys.argv[1:]:

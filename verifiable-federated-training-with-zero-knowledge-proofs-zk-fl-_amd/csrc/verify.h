@@ -59,5 +59,31 @@ constexpr size_t ROUND_MAX_CHUNK = 65536;
 int verify_round(size_t n, const VerifyJob* jobs, const uint8_t* proofs, const uint8_t* z, size_t chunk,
                  uint8_t* gt_out, int32_t* screened, int* passed, uint32_t* nkeys, hipStream_t st, Profiler* prof,
                  std::string& err);
+// Jobs per pass: min(n, chunk), chunk 0 = 4096 (4096 x 102 lines x 192 B = 80 MB of lines, as
+// verify_batch)
+inline size_t round_pass_size(size_t n, size_t chunk) {
+  if (chunk == 0) chunk = 4096;
+  if (chunk > ROUND_MAX_CHUNK) chunk = ROUND_MAX_CHUNK;
+  return n < chunk ? n : chunk;
+}
+// Groups of `group` consecutive jobs (>= 1) of every pass, the last one of a pass may be short
+inline size_t round_group_count(size_t n, size_t chunk, size_t group) {
+  const size_t pass = round_pass_size(n, chunk);
+  if (pass == 0) return 0;
+  return (n / pass) * ((pass + group - 1) / group) + (n % pass + group - 1) / group;
+}
+// verify_round with one value per group: the passes' jobs in verify_round's order (by key,
+// stable) are cut into runs of `group` (1 .. round_pass_size), and every group's Miller value --
+// its jobs' pairs and the three pairs of each of its key segments' own sums -- is kept on the
+// device.  The round's value is the product of the groups' values: *passed as verify_round's.
+// The groups' values are exponentiated in one launch, one wavefront each, when the round fails and
+// at least narrow_min jobs passed the screening, or always when gt_groups is not null; *narrowed
+// says whether they were.  Then group_one[g] = (group g's value == 1) and gt_groups (nullable)
+// holds the values, 384 B each.  group_of[i] (n entries): job i's group, counted across passes.
+// prof: verify_round's records and "verify_round_groups".
+int verify_round_narrow(size_t n, const VerifyJob* jobs, const uint8_t* proofs, const uint8_t* z, size_t chunk,
+                        size_t group, size_t narrow_min, uint32_t* group_of, std::vector<uint8_t>* group_one,
+                        std::vector<uint8_t>* gt_groups, int32_t* screened, int* passed, int* narrowed,
+                        uint32_t* nkeys, hipStream_t st, Profiler* prof, std::string& err);
 
 }  // namespace zkfl

@@ -185,10 +185,12 @@ __global__ __launch_bounds__(64) void k_round_screen(size_t m, unsigned gb, size
 // Block (k, y): sum y (0 S, 1 X, 2 C) of key k over the pass's jobs [lo, hi) -- for X their term
 // groups [xlo, xhi) -- that passed the screening, added to acc[k][y] (stored when first).  Lanes
 // stride over the range, then a tree over the lanes.
-__global__ __launch_bounds__(SUM_THREADS) void k_round_sums(size_t m, const RoundRange* ranges,
-                                                            const RoundGroup* groups, const uint32_t* bstat,
-                                                            const uint32_t* gstat, const G1P* sums, int first,
-                                                            G1P* acc, int32_t* screened) {
+// The narrow entry runs it per segment (a group's jobs of one key) with a tree of one wavefront.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_round_sums(size_t m, const RoundRange* ranges, const RoundGroup* groups,
+                                                        const uint32_t* bstat, const uint32_t* gstat, const G1P* sums,
+                                                        int first, G1P* acc, int32_t* screened) {
+  constexpr unsigned SUM_THREADS = THREADS;
   __shared__ G1P s[SUM_THREADS];
   const unsigned k = blockIdx.x, y = blockIdx.y, t = threadIdx.x;
   const RoundRange rg = ranges[k];
@@ -300,7 +302,78 @@ __global__ __launch_bounds__(64) void k_round_final(const Fq12* f, uint32_t* gt_
   if (threadIdx.x == 0) *passed = wv_is_one(&s, 0) ? 1u : 0u;
 }
 
+// ---- narrowing: one value per group of jobs (verify_round_narrow) ----
+// A group is a run of jobs of the pass; a segment is a group's jobs of one key, with sums S, X, C
+// of its own (k_round_sums over the segment's range) and three pairs against that key's lines
+// (k_round_pair's items behind the jobs).  jlo..jhi: the group's jobs, slo..shi: its segments.
+struct RoundGrp {
+  uint32_t jlo, jhi, slo, shi;
+};
+
+// Block g: out[g] = the product of both Miller parts of group g's jobs and of its segments' three
+// pairs, f laid out as k_round_pair writes it.  Lanes stride over the 2 (jobs + 3 segments)
+// values, then a tree over the lanes.
+__global__ __launch_bounds__(64) void k_round_group_prod(size_t m, size_t nk3, const RoundGrp* grps, const Fq12* f,
+                                                         Fq12* out) {
+  __shared__ Fq12 s[64];
+  const unsigned t = threadIdx.x;
+  const RoundGrp g = grps[blockIdx.x];
+  const size_t nj = g.jhi - g.jlo, per = nj + (size_t)ROUND_NSUM * (g.shi - g.slo);
+  Fq12 a = f12_one();
+  bool have = false;
+  for (size_t e = t; e < 2 * per; e += 64) {
+    const size_t part = e >= per ? 1 : 0, r = e - part * per;
+    const size_t item = r < nj ? g.jlo + r : m + (size_t)ROUND_NSUM * g.slo + (r - nj);
+    const Fq12 v = f[part * (m + nk3) + item];
+    a = have ? f12_mul(a, v) : v;
+    have = true;
+  }
+  s[t] = a;
+  __syncthreads();
+  for (unsigned h = 32; h > 0; h >>= 1) {
+    if (t < h) {
+      const Fq12 p = s[t], q = s[t + h];
+      s[t] = f12_mul(p, q);
+    }
+    __syncthreads();
+  }
+  if (t == 0) out[blockIdx.x] = s[0];
+}
+
+// k_round_final, one wavefront per group: gt of group g at gt_std + 96 g, one[g] = (gt == 1)
+__global__ __launch_bounds__(64) void k_round_final_groups(const Fq12* f, uint32_t* gt_std, uint32_t* one) {
+  __shared__ WaveLds s;
+  const size_t g = blockIdx.x;
+  wv_load_f12(&s, 0, f + g);
+  wv_final_exp(&s);
+  wv_store_std(&s, 0, gt_std + 96 * g);
+  if (threadIdx.x == 0) one[g] = wv_is_one(&s, 0) ? 1u : 0u;
+}
+
 constexpr size_t PAD = 16;  // bytes behind every allocation of this unit
+
+// keys in order of first appearance; jobs ordered by key (stable), so a key's jobs are one range
+// [start[k], start[k + 1]) of order
+void round_order(size_t n, const VerifyJob* jobs, std::vector<const VkDev*>& keys, std::vector<uint32_t>& key_of,
+                 std::vector<size_t>& start, std::vector<size_t>& order) {
+  key_of.resize(n);
+  std::unordered_map<const VkDev*, uint32_t> seen;
+  for (size_t i = 0; i < n; i++) {
+    auto it = seen.find(jobs[i].vk);
+    if (it == seen.end()) {
+      it = seen.emplace(jobs[i].vk, (uint32_t)keys.size()).first;
+      keys.push_back(jobs[i].vk);
+    }
+    key_of[i] = it->second;
+  }
+  const size_t K = keys.size();
+  start.assign(K + 1, 0);
+  order.resize(n);
+  for (size_t i = 0; i < n; i++) start[key_of[i] + 1]++;
+  for (size_t k = 0; k < K; k++) start[k + 1] += start[k];
+  std::vector<size_t> fill(start.begin(), start.end() - 1);
+  for (size_t i = 0; i < n; i++) order[fill[key_of[i]]++] = i;
+}
 
 }  // namespace
 
@@ -308,32 +381,13 @@ int verify_round(size_t n, const VerifyJob* jobs, const uint8_t* proofs, const u
                  uint8_t* gt_out, int32_t* screened, int* passed, uint32_t* nkeys, hipStream_t st, Profiler* prof,
                  std::string& err) {
   const char* const where = "verify_round";
-  // keys in order of first appearance; jobs ordered by key (stable), so a key's jobs are one range
   std::vector<const VkDev*> keys;
-  std::vector<uint32_t> key_of(n);
-  {
-    std::unordered_map<const VkDev*, uint32_t> seen;
-    for (size_t i = 0; i < n; i++) {
-      auto it = seen.find(jobs[i].vk);
-      if (it == seen.end()) {
-        it = seen.emplace(jobs[i].vk, (uint32_t)keys.size()).first;
-        keys.push_back(jobs[i].vk);
-      }
-      key_of[i] = it->second;
-    }
-  }
+  std::vector<uint32_t> key_of;
+  std::vector<size_t> start, order;
+  round_order(n, jobs, keys, key_of, start, order);
   const size_t K = keys.size();
   if (nkeys) *nkeys = (uint32_t)K;
-  std::vector<size_t> start(K + 1, 0), order(n);
-  for (size_t i = 0; i < n; i++) start[key_of[i] + 1]++;
-  for (size_t k = 0; k < K; k++) start[k + 1] += start[k];
-  {
-    std::vector<size_t> fill(start.begin(), start.end() - 1);
-    for (size_t i = 0; i < n; i++) order[fill[key_of[i]]++] = i;
-  }
-  if (chunk == 0) chunk = 4096;  // 4096 x 102 lines x 192 B = 80 MB of lines, as verify_batch
-  if (chunk > ROUND_MAX_CHUNK) chunk = ROUND_MAX_CHUNK;
-  const size_t cap = n < chunk ? n : chunk;
+  const size_t cap = round_pass_size(n, chunk);
   size_t pub_words = 0, tcap = 0;  // the largest pass: public signals, term groups
   for (size_t off = 0; off < n; off += cap) {
     size_t w = 0, t = 0;
@@ -425,7 +479,7 @@ int verify_round(size_t n, const VerifyJob* jobs, const uint8_t* proofs, const u
                        (const uint32_t*)d_proof, (const uint32_t*)d_z, d_lines, d_bstat, d_gstat, d_P0, d_sums);
     if (prof) prof->end(pi, st, (double)m);
     pi = prof ? prof->begin("verify_round_reduce", st) : -1;
-    hipLaunchKernelGGL(k_round_sums, dim3((unsigned)K, ROUND_NSUM), dim3(SUM_THREADS), 0, st, m,
+    hipLaunchKernelGGL(k_round_sums<SUM_THREADS>, dim3((unsigned)K, ROUND_NSUM), dim3(SUM_THREADS), 0, st, m,
                        (const RoundRange*)d_ranges, (const RoundGroup*)d_groups, (const uint32_t*)d_bstat, (const uint32_t*)d_gstat,
                        (const G1P*)d_sums, first ? 1 : 0, d_acc, d_scr);
     if (prof) prof->end(pi, st, (double)m);
@@ -470,6 +524,200 @@ int verify_round(size_t n, const VerifyJob* jobs, const uint8_t* proofs, const u
   HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
   if (gt_out) memcpy(gt_out, hgt, 384);
   if (passed) *passed = (int)hpass;
+  return ZKFL_OK;
+}
+
+// verify_round's passes with the sums and the three pairs per segment instead of per key: the
+// pairs ride in every pass's own pair launch, k_round_group_prod forms the groups' values and the
+// round's value is their product, so a passing round launches what verify_round launches plus
+// nothing of length, and a failing one only adds k_round_final_groups.  FE(prod ML(S_g, beta)) =
+// FE(ML(sum S_g, beta)) and all arithmetic is exact: the round's 384 B are verify_round's.
+int verify_round_narrow(size_t n, const VerifyJob* jobs, const uint8_t* proofs, const uint8_t* z, size_t chunk,
+                        size_t group, size_t narrow_min, uint32_t* group_of, std::vector<uint8_t>* group_one,
+                        std::vector<uint8_t>* gt_groups, int32_t* screened, int* passed, int* narrowed,
+                        uint32_t* nkeys, hipStream_t st, Profiler* prof, std::string& err) {
+  const char* const where = "verify_round_narrow";
+  std::vector<const VkDev*> keys;
+  std::vector<uint32_t> key_of;
+  std::vector<size_t> start, order;
+  round_order(n, jobs, keys, key_of, start, order);
+  if (nkeys) *nkeys = (uint32_t)keys.size();
+  const size_t cap = round_pass_size(n, chunk);
+  if (group == 0 || group > cap) {
+    err = std::string(where) + ": group size outside 1 .. the pass size";
+    return ZKFL_E_ARG;
+  }
+  const size_t G = round_group_count(n, chunk, group), gcap = (cap + group - 1) / group;
+  // a segment starts with every group and at every change of key inside one
+  auto seg_starts = [&](size_t off, size_t j) {
+    return j % group == 0 || key_of[order[off + j]] != key_of[order[off + j - 1]];
+  };
+  size_t pub_words = 0, tcap = 0, scap = 0;  // the largest pass: public signals, term groups, segments
+  for (size_t off = 0; off < n; off += cap) {
+    size_t w = 0, t = 0, s = 0;
+    for (size_t j = 0; off + j < n && j < cap; j++) {
+      const size_t np = jobs[order[off + j]].vk->npub;
+      w += 8 * np;
+      t += (np + 1 + ROUND_TERMS - 1) / ROUND_TERMS;
+      if (seg_starts(off, j)) s++;
+    }
+    if (w > pub_words) pub_words = w;
+    if (t > tcap) tcap = t;
+    if (s > scap) scap = s;
+  }
+  const size_t tree = (G + 63) / 64;  // the first level of the product over the groups' values
+
+  DevBufs D;
+  RoundJobDev* d_jobs;
+  RoundRange* d_segs;
+  RoundGroup* d_groups;
+  RoundGrp* d_grps;
+  const LineCoef** d_slines;
+  uint32_t *d_pub, *d_proof, *d_z, *d_bstat, *d_gstat, *d_gt, *d_pass, *d_ggt, *d_gone;
+  LineCoef* d_lines;
+  G1Aff* d_P0;
+  G1P *d_sums, *d_acc;
+  int32_t* d_scr;
+  Fq12 *d_f, *d_gval, *d_fa, *d_fb;
+  HIP_TRY_ERR(D.get(&d_jobs, cap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_segs, scap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_groups, tcap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_grps, gcap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_slines, scap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_pub, pub_words, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_proof, cap * 64, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_z, cap * 4, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_bstat, cap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_gstat, 2 * cap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_gt, 96, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_pass, 1, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_ggt, 96 * G, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_gone, G, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_lines, cap * ATE_NLINES, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_P0, cap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_sums, 2 * cap + tcap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_acc, ROUND_NSUM * scap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_scr, cap, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_f, 2 * (cap + ROUND_NSUM * scap), PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_gval, G, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_fa, tree, PAD), where, err);
+  HIP_TRY_ERR(D.get(&d_fb, (tree + 63) / 64, PAD), where, err);
+
+  std::vector<RoundJobDev> hj(cap);
+  std::vector<RoundRange> hs(scap);
+  std::vector<const LineCoef*> hsl(scap);
+  std::vector<RoundGrp> hgr(gcap);
+  std::vector<RoundGroup> hg(tcap);
+  std::vector<size_t> gfirst(cap + 1);  // job j's first term group
+  std::vector<uint32_t> hpub(pub_words + 1), hproof(cap * 64), hz(cap * 4);
+  std::vector<int32_t> hscr(cap);
+  size_t gbase = 0, combined = 0;  // the groups of earlier passes; jobs that passed the screening
+  for (size_t off = 0; off < n; off += cap) {
+    const size_t m = (n - off < cap) ? n - off : cap;
+    const size_t ng = (m + group - 1) / group;
+    size_t w = 0, T = 0, S = 0;
+    for (size_t j = 0; j < m; j++) {
+      const size_t i = order[off + j];
+      const VkDev* vk = jobs[i].vk;
+      hj[j] = {vk->ic_table, vk->alpha, (uint64_t)w, vk->npub, 0};
+      gfirst[j] = T;
+      for (uint32_t t0 = 0; t0 < vk->npub + 1; t0 += ROUND_TERMS) hg[T++] = {(uint32_t)j, t0};
+      if (vk->npub) memcpy(hpub.data() + w, jobs[i].pub, 32 * (size_t)vk->npub);
+      w += 8 * (size_t)vk->npub;
+      memcpy(hproof.data() + 64 * j, proofs + 256 * i, 256);
+      memcpy(hz.data() + 4 * j, z + 16 * i, 16);
+      if (j % group == 0) hgr[j / group] = {(uint32_t)j, (uint32_t)j, (uint32_t)S, (uint32_t)S};
+      if (seg_starts(off, j)) {
+        hs[S] = {(uint32_t)j, (uint32_t)j, 0, 0};  // the term groups' range follows below
+        hsl[S] = vk->lines;
+        S++;
+        hgr[j / group].shi = (uint32_t)S;
+      }
+      hs[S - 1].hi = (uint32_t)(j + 1);
+      hgr[j / group].jhi = (uint32_t)(j + 1);
+      group_of[i] = (uint32_t)(gbase + j / group);
+    }
+    gfirst[m] = T;
+    for (size_t s = 0; s < S; s++) {
+      hs[s].xlo = (uint32_t)gfirst[hs[s].lo];
+      hs[s].xhi = (uint32_t)gfirst[hs[s].hi];
+    }
+    HIP_TRY_ERR(hipMemcpyAsync(d_jobs, hj.data(), m * sizeof(RoundJobDev), hipMemcpyHostToDevice, st), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(d_segs, hs.data(), S * sizeof(RoundRange), hipMemcpyHostToDevice, st), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(d_slines, hsl.data(), S * sizeof(LineCoef*), hipMemcpyHostToDevice, st), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(d_grps, hgr.data(), ng * sizeof(RoundGrp), hipMemcpyHostToDevice, st), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(d_groups, hg.data(), T * sizeof(RoundGroup), hipMemcpyHostToDevice, st), where, err);
+    if (w) HIP_TRY_ERR(hipMemcpyAsync(d_pub, hpub.data(), w * 4, hipMemcpyHostToDevice, st), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(d_proof, hproof.data(), m * 256, hipMemcpyHostToDevice, st), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(d_z, hz.data(), m * 16, hipMemcpyHostToDevice, st), where, err);
+
+    const unsigned gb = zk_grid(m, 64);
+    int pi = prof ? prof->begin("verify_round_screen", st) : -1;
+    hipLaunchKernelGGL(k_round_screen, dim3(4 * gb + zk_grid(T, 64)), dim3(64), 0, st, m, gb, T,
+                       (const RoundJobDev*)d_jobs, (const RoundGroup*)d_groups, (const uint32_t*)d_pub,
+                       (const uint32_t*)d_proof, (const uint32_t*)d_z, d_lines, d_bstat, d_gstat, d_P0, d_sums);
+    if (prof) prof->end(pi, st, (double)m);
+    pi = prof ? prof->begin("verify_round_reduce", st) : -1;
+    hipLaunchKernelGGL(k_round_sums<64>, dim3((unsigned)S, ROUND_NSUM), dim3(64), 0, st, m, (const RoundRange*)d_segs,
+                       (const RoundGroup*)d_groups, (const uint32_t*)d_bstat, (const uint32_t*)d_gstat,
+                       (const G1P*)d_sums, 1, d_acc, d_scr);
+    if (prof) prof->end(pi, st, (double)m);
+    const size_t nk3 = ROUND_NSUM * S;
+    pi = prof ? prof->begin("verify_round_pair", st) : -1;
+    const unsigned gk = zk_grid(nk3, 64);
+    hipLaunchKernelGGL(k_round_pair, dim3(2 * (gb + gk)), dim3(64), 0, st, m, gb, (const G1Aff*)d_P0,
+                       (const LineCoef*)d_lines, (const uint32_t*)d_bstat, (const uint32_t*)d_gstat, nk3, gk,
+                       (const G1P*)d_acc, (const LineCoef* const*)d_slines, d_f);
+    if (prof) prof->end(pi, st, (double)m);
+    pi = prof ? prof->begin("verify_round_reduce", st) : -1;
+    hipLaunchKernelGGL(k_round_group_prod, dim3((unsigned)ng), dim3(64), 0, st, m, nk3, (const RoundGrp*)d_grps,
+                       (const Fq12*)d_f, d_gval + gbase);
+    if (prof) prof->end(pi, st, 0.0);
+    HIP_TRY_ERR(hipGetLastError(), where, err);
+    HIP_TRY_ERR(hipMemcpyAsync(hscr.data(), d_scr, m * 4, hipMemcpyDeviceToHost, st), where, err);
+    HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
+    for (size_t j = 0; j < m; j++) {
+      screened[order[off + j]] = hscr[j];
+      if (!hscr[j]) combined++;
+    }
+    gbase += ng;
+  }
+  // the round's value: the product of the groups' values, which stay where they are
+  const Fq12* in = d_gval;
+  Fq12 *out = d_fa, *other = d_fb;
+  int pi = prof ? prof->begin("verify_round_reduce", st) : -1;
+  for (size_t cnt = G; cnt > 1;) {
+    const unsigned g = zk_grid(cnt, 64);
+    hipLaunchKernelGGL(k_round_prod, dim3(g), dim3(64), 0, st, cnt, in, out);
+    cnt = g;
+    in = out;
+    out = other;
+    other = const_cast<Fq12*>(in);
+  }
+  if (prof) prof->end(pi, st, 0.0);
+  pi = prof ? prof->begin("verify_round_final", st) : -1;
+  hipLaunchKernelGGL(k_round_final, dim3(1), dim3(64), 0, st, in, d_gt, d_pass);
+  if (prof) prof->end(pi, st, (double)n);
+  HIP_TRY_ERR(hipGetLastError(), where, err);
+  uint32_t hpass = 0;
+  HIP_TRY_ERR(hipMemcpyAsync(&hpass, d_pass, 4, hipMemcpyDeviceToHost, st), where, err);
+  HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
+  if (passed) *passed = (int)hpass;
+  const bool narrow = gt_groups || (!hpass && combined >= narrow_min);
+  if (narrowed) *narrowed = narrow ? 1 : 0;
+  if (!narrow) return ZKFL_OK;
+  pi = prof ? prof->begin("verify_round_groups", st) : -1;
+  hipLaunchKernelGGL(k_round_final_groups, dim3((unsigned)G), dim3(64), 0, st, (const Fq12*)d_gval, d_ggt, d_gone);
+  if (prof) prof->end(pi, st, (double)G);
+  HIP_TRY_ERR(hipGetLastError(), where, err);
+  std::vector<uint32_t> hone(G);
+  HIP_TRY_ERR(hipMemcpyAsync(hone.data(), d_gone, G * 4, hipMemcpyDeviceToHost, st), where, err);
+  if (gt_groups) {
+    gt_groups->resize(384 * G);
+    HIP_TRY_ERR(hipMemcpyAsync(gt_groups->data(), d_ggt, 384 * G, hipMemcpyDeviceToHost, st), where, err);
+  }
+  HIP_TRY_ERR(hipStreamSynchronize(st), where, err);
+  group_one->assign(hone.begin(), hone.end());
   return ZKFL_OK;
 }
 

@@ -700,21 +700,26 @@ int zkfl_groth16_verify_multi(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* v
   return verify_multi_run(ctx, n, vkeys, pubs, proofs, results, schedule);
 }
 
+// z NULL: n x 16 B from the OS CSPRNG into drawn, as rs == NULL for proofs; every 128-bit value is a valid z
+static int round_draw_z(size_t n, const uint8_t*& z, std::vector<uint8_t>& drawn) {
+  if (z) return ZKFL_OK;
+  drawn.resize(16 * n);
+  for (size_t got = 0; got < drawn.size();) {
+    const size_t want = std::min<size_t>(256, drawn.size() - got);
+    if (getrandom(drawn.data() + got, want, 0) != (ssize_t)want) return fail(ZKFL_E_DEVICE, "getrandom failed");
+    got += want;
+  }
+  z = drawn.data();
+  return ZKFL_OK;
+}
+
 // A round as one random combination (csrc/verify_round.hip).  screened: n flags; *passed: the
 // combination is 1.
 static int verify_round_combine(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
                                 const uint8_t* proofs, const uint8_t* z, size_t chunk, uint8_t* gt_out,
                                 int32_t* screened, int* passed, uint32_t* nkeys) {
   std::vector<uint8_t> drawn;
-  if (!z) {  // CSPRNG, as rs == NULL for proofs; every 128-bit value is a valid z
-    drawn.resize(16 * n);
-    for (size_t got = 0; got < drawn.size();) {
-      const size_t want = std::min<size_t>(256, drawn.size() - got);
-      if (getrandom(drawn.data() + got, want, 0) != (ssize_t)want) return fail(ZKFL_E_DEVICE, "getrandom failed");
-      got += want;
-    }
-    z = drawn.data();
-  }
+  if (const int rc = round_draw_z(n, z, drawn)) return rc;
   std::vector<VerifyJob> jobs(n);
   for (size_t i = 0; i < n; i++) jobs[i] = {vkeys[i]->vk, vkeys[i]->wtab, pubs[i]};
   std::string err;
@@ -780,6 +785,117 @@ int zkfl_debug_verify_round(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vke
   int passed = 0;
   const int rc = verify_round_combine(ctx, n, vkeys, pubs, proofs, z, chunk, gt_out, screened.data(), &passed, nullptr);
   if (rc != ZKFL_OK) return rc;
+  memcpy(screened_out, screened.data(), n * sizeof(int32_t));
+  return ZKFL_OK;
+}
+
+int zkfl_groth16_verify_round_narrow(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys,
+                                     const uint8_t* const* pubs, const size_t* npubs, const uint8_t* proofs,
+                                     const uint8_t* z, uint32_t group, int32_t* results, zkfl_narrow_report* report) {
+  if (!ctx || (n && (!vkeys || !pubs || !npubs || !proofs || !results)))
+    return fail(ZKFL_E_ARG, "verify_round_narrow: null argument");
+  if (const int rc = verify_jobs_check("verify_round_narrow", ctx, n, vkeys, pubs, npubs)) return rc;
+  zkfl_narrow_report rep = {0, 0, 0, 1, 0, 0, 0};
+  if (n == 0) {
+    if (report) *report = rep;
+    return ZKFL_OK;
+  }
+  const size_t pass = round_pass_size(n, 0);
+  if (group > pass)
+    return fail(ZKFL_E_ARG, "verify_round_narrow: group " + std::to_string(group) + " exceeds the pass of " +
+                                std::to_string(pass) + " jobs");
+  if (group == 0 && n < ZKFL_ROUND_NARROW_MIN) {  // too small to narrow, whatever is screened: the plain call
+    zkfl_round_report r5;
+    const int rc = zkfl_groth16_verify_round(ctx, n, vkeys, pubs, npubs, proofs, z, results, &r5);
+    if (rc != ZKFL_OK) return rc;
+    rep = {r5.keys, r5.screened, r5.combined, r5.passed, 0, 0, r5.fallback};
+    if (report) *report = rep;
+    return ZKFL_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  std::vector<uint8_t> drawn, group_one;
+  if (const int rc = round_draw_z(n, z, drawn)) return rc;
+  std::vector<VerifyJob> jobs(n);
+  for (size_t i = 0; i < n; i++) jobs[i] = {vkeys[i]->vk, vkeys[i]->wtab, pubs[i]};
+  std::vector<int32_t> screened(n, 0), res(n, 0);
+  std::vector<uint32_t> group_of(n, 0);
+  int passed = 0, narrowed = 0;
+  std::string err;
+  const size_t gsize = group ? group : std::min<size_t>(ZKFL_ROUND_GROUP, pass);
+  int rc = verify_round_narrow(n, jobs.data(), proofs, z, 0, gsize, group ? 0 : ZKFL_ROUND_NARROW_MIN, group_of.data(),
+                               &group_one, nullptr, screened.data(), &passed, &narrowed, &rep.keys, ctx->st,
+                               &ctx->prof, err);
+  if (rc != ZKFL_OK) return fail(rc, err);
+  std::vector<size_t> again;  // the jobs to verify one by one
+  for (size_t i = 0; i < n; i++) {
+    if (screened[i]) continue;
+    rep.combined++;
+    if (passed || (narrowed && group_one[group_of[i]]))
+      res[i] = 1;
+    else
+      again.push_back(i);
+  }
+  rep.screened = (uint32_t)n - rep.combined;
+  rep.passed = passed ? 1 : 0;
+  if (passed || narrowed) rep.groups = (uint32_t)round_group_count(n, 0, gsize);
+  if (narrowed)
+    for (uint8_t one : group_one) rep.bad_groups += one ? 0 : 1;
+  if (!again.empty()) {
+    const size_t m = again.size();
+    std::vector<const zkfl_vkey*> fk(m);
+    std::vector<const uint8_t*> fp(m);
+    std::vector<uint8_t> fpr(256 * m);
+    std::vector<int32_t> fres(m, 0);
+    for (size_t j = 0; j < m; j++) {
+      fk[j] = vkeys[again[j]];
+      fp[j] = pubs[again[j]];
+      memcpy(fpr.data() + 256 * j, proofs + 256 * again[j], 256);
+    }
+    rc = verify_multi_run(ctx, m, fk.data(), fp.data(), fpr.data(), fres.data(), ZKFL_VERIFY_AUTO);
+    if (rc != ZKFL_OK) return rc;
+    for (size_t j = 0; j < m; j++) res[again[j]] = fres[j];
+    rep.fallback = (uint32_t)m;
+  }
+  memcpy(results, res.data(), n * sizeof(int32_t));
+  if (report) *report = rep;
+  return ZKFL_OK;
+}
+
+int zkfl_debug_verify_round_groups(zkfl_ctx* ctx, size_t n, const zkfl_vkey* const* vkeys, const uint8_t* const* pubs,
+                                   const size_t* npubs, const uint8_t* proofs, const uint8_t* z, size_t chunk,
+                                   uint32_t group, uint32_t* group_of, uint8_t* gt_groups, size_t cap,
+                                   uint32_t* n_groups, int32_t* screened_out) {
+  if (!ctx || !n_groups ||
+      (n && (!vkeys || !pubs || !npubs || !proofs || !z || !group_of || !gt_groups || !screened_out)))
+    return fail(ZKFL_E_ARG, "verify_round_groups: null argument");
+  if (const int rc = verify_jobs_check("verify_round_groups", ctx, n, vkeys, pubs, npubs)) return rc;
+  if (n == 0) {
+    *n_groups = 0;
+    return ZKFL_OK;
+  }
+  const size_t pass = round_pass_size(n, chunk);
+  if (group > pass)
+    return fail(ZKFL_E_ARG, "verify_round_groups: group " + std::to_string(group) + " exceeds the pass of " +
+                                std::to_string(pass) + " jobs");
+  const size_t gsize = group ? group : std::min<size_t>(ZKFL_ROUND_GROUP, pass);
+  const size_t G = round_group_count(n, chunk, gsize);
+  *n_groups = (uint32_t)G;
+  if (cap < G)
+    return fail(ZKFL_E_ARG, "verify_round_groups: room for " + std::to_string(cap) + " of " + std::to_string(G) +
+                                " groups");
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  std::vector<VerifyJob> jobs(n);
+  for (size_t i = 0; i < n; i++) jobs[i] = {vkeys[i]->vk, vkeys[i]->wtab, pubs[i]};
+  std::vector<int32_t> screened(n, 0);
+  std::vector<uint32_t> gof(n, 0);
+  std::vector<uint8_t> group_one, gt;
+  int passed = 0, narrowed = 0;
+  std::string err;
+  const int rc = verify_round_narrow(n, jobs.data(), proofs, z, chunk, gsize, 0, gof.data(), &group_one, &gt,
+                                     screened.data(), &passed, &narrowed, nullptr, ctx->st, &ctx->prof, err);
+  if (rc != ZKFL_OK) return fail(rc, err);
+  memcpy(group_of, gof.data(), n * sizeof(uint32_t));
+  memcpy(gt_groups, gt.data(), 384 * G);
   memcpy(screened_out, screened.data(), n * sizeof(int32_t));
   return ZKFL_OK;
 }

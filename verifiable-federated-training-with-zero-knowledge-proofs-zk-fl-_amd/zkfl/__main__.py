@@ -36,6 +36,9 @@
         --combined: answer the round by one random combination with one final exponentiation
         (verify_round; the per-proof path gives the verdicts when it fails).  Same lines and exit
         codes; the report goes to stderr
+        --narrow: --combined, and when the combination fails the round is narrowed to the groups of jobs
+        whose own combination fails; only those go to the per-proof path (verify_round_narrow).  Same
+        lines and exit codes; the narrow report goes to stderr
     python -m zkfl aggregate-round <round.json>              aggregateUpdates (:1137-1199) with the masks of the
         excluded clients taken out.  round.json: {"round", "dim", "groups": [{"clients": [{"id",
         "accepted", "public"}], "revealed": [{"in", "out", "key"}]}]}; "public" is an accepted client's
@@ -259,7 +262,11 @@ def cmd_verify_round(args):
             if vpath not in handles:
                 handles[vpath] = p.load_vkey(vk)
         round_jobs = [(handles[j[0]], d[1], d[2]) for j, d in zip(jobs, data)]
-        if args.combined:
+        if args.narrow:
+            oks, rep = p.verify_round_narrow(round_jobs)
+            print("[INFO]  zkfl: combined round, narrowed: " + ", ".join(f"{k} {v}" for k, v in rep.items()),
+                  file=sys.stderr)
+        elif args.combined:
             oks, rep = p.verify_round(round_jobs)
             print("[INFO]  zkfl: combined round: " + ", ".join(f"{k} {v}" for k, v in rep.items()), file=sys.stderr)
         else:
@@ -570,6 +577,8 @@ def main(argv=None):
     sp.add_argument("round")
     sp.add_argument("--combined", action="store_true",
                     help="one random combination and one final exponentiation for the whole round")
+    sp.add_argument("--narrow", action="store_true",
+                    help="--combined, and a failed round is narrowed to its bad groups before the per-proof path")
     sp = sub.add_parser("aggregate-round")
     sp.add_argument("round")
     sp = sub.add_parser("admit-round")

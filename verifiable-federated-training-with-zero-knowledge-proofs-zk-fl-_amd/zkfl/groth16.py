@@ -214,6 +214,14 @@ class Prover:
             [(vk if isinstance(vk, native.VerifyingKey) else self.load_vkey(vk), public_bytes(pub),
               proof_from_json(proof)) for vk, pub, proof in jobs], z)
 
+    def verify_round_narrow(self, jobs, z=None, group: int = 0):
+        """verify_round's jobs and verdicts -> ([bool], narrow report dict); a failed round is
+        narrowed to the groups whose own combination fails, and only their jobs go to the
+        per-proof path (Context.verify_round_narrow).  group 0: the production policy."""
+        return self.ctx.verify_round_narrow(
+            [(vk if isinstance(vk, native.VerifyingKey) else self.load_vkey(vk), public_bytes(pub),
+              proof_from_json(proof)) for vk, pub, proof in jobs], z, group)
+
     def close(self):
         for k in list(self._keys.values()) + list(self._vkeys.values()):
             k.close()
@@ -295,6 +303,11 @@ def verify_round(jobs, z=None):
     return _prover().verify_round(jobs, z)
 
 
-__all__ = ["prove", "fullProve", "verify", "verify_multi", "verify_round", "load_vkey", "Prover", "proof_to_json", "proof_from_json", "export_verification_key",
+def verify_round_narrow(jobs, z=None, group: int = 0):
+    """verify_round with a failed round narrowed to its bad groups (Prover.verify_round_narrow)."""
+    return _prover().verify_round_narrow(jobs, z, group)
+
+
+__all__ = ["prove", "fullProve", "verify", "verify_multi", "verify_round", "verify_round_narrow", "load_vkey", "Prover", "proof_to_json", "proof_from_json", "export_verification_key",
            "vk_bytes", "public_bytes", "wtns_calculate", "r1cs_info", "read_wtns", "wtns_check",
            "wtns_check_report", "zkey_check", "ptau_check"]

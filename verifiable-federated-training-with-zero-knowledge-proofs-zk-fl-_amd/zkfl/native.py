@@ -246,6 +246,13 @@ SIGNATURES = {
     "zkfl_debug_verify_round": (C.c_int, [_P, C.c_size_t, C.POINTER(_P), C.POINTER(C.c_char_p),
                                           C.POINTER(C.c_size_t), C.c_char_p, C.c_char_p, C.c_size_t, _U8P,
                                           C.POINTER(C.c_int32)]),
+    "zkfl_groth16_verify_round_narrow": (C.c_int, [_P, C.c_size_t, C.POINTER(_P), C.POINTER(C.c_char_p),
+                                                   C.POINTER(C.c_size_t), C.c_char_p, C.c_char_p, C.c_uint32,
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
+    "zkfl_debug_verify_round_groups": (C.c_int, [_P, C.c_size_t, C.POINTER(_P), C.POINTER(C.c_char_p),
+                                                 C.POINTER(C.c_size_t), C.c_char_p, C.c_char_p, C.c_size_t,
+                                                 C.c_uint32, C.POINTER(C.c_uint32), _U8P, C.c_size_t,
+                                                 C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "zkfl_debug_wave_pairing": (C.c_int,[_P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_int, _U8P]),
     "zkfl_wprog_load": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(_P)]),
     "zkfl_wprog_free": (C.c_int, [_P]),
@@ -711,6 +718,34 @@ class Context(_Handle):
         check(lib().zkfl_debug_verify_round(self.h, n, keys, pubs, npubs, proofs, z, chunk, out, scr))
         return bytes(out)[:384], [bool(scr[i]) for i in range(n)]
 
+    def verify_round_narrow(self, jobs, z=None, group: int = 0):
+        """verify_round with a failed round narrowed to its bad groups
+        (zkfl_groth16_verify_round_narrow): the passes' jobs, sorted by key, are cut into groups of
+        `group`, every group gets a value of its own, and only the jobs of the groups whose value
+        is not 1 are re-verified -> ([bool] in job order, report dict: NARROW_REPORT_FIELDS).
+        group 0: the production policy (groups of ROUND_GROUP, narrowing from ROUND_NARROW_MIN
+        combined jobs on).  z as in verify_round."""
+        n, keys, pubs, npubs, proofs, z = self._round_args(jobs, z)
+        res = (C.c_int32 * max(1, n))()
+        rep = (C.c_uint32 * len(NARROW_REPORT_FIELDS))()
+        check(lib().zkfl_groth16_verify_round_narrow(self.h, n, keys, pubs, npubs, proofs, z, group, res, rep))
+        return [bool(res[i]) for i in range(n)], dict(zip(NARROW_REPORT_FIELDS, (int(v) for v in rep)))
+
+    def debug_verify_round_groups(self, jobs, z, chunk: int = 0, group: int = 0):
+        """The parity hook of verify_round_narrow -> ([job i's group], [every group's
+        final-exponentiated value, 384 B in pairing()'s layout], [bool] screened per job)."""
+        n, keys, pubs, npubs, proofs, z = self._round_args(jobs, z)
+        cap = max(1, n)  # a group holds at least one job
+        group_of = (C.c_uint32 * cap)()
+        out = _buf(384 * cap)
+        scr = (C.c_int32 * cap)()
+        ng = C.c_uint32(0)
+        check(lib().zkfl_debug_verify_round_groups(self.h, n, keys, pubs, npubs, proofs, z, chunk, group, group_of,
+                                                   out, cap, C.byref(ng), scr))
+        raw = bytes(out)
+        return ([int(group_of[i]) for i in range(n)], [raw[384 * g:384 * (g + 1)] for g in range(ng.value)],
+                [bool(scr[i]) for i in range(n)])
+
     def wave_pairing(self, g1: bytes, g2: bytes, final_exp: bool = True) -> bytes:
         """pairing() computed by the wave verifier's tower, Miller loop and final exponentiation
         (one pair per wavefront): the parity hook of Context.verify_multi's "waves" schedule."""
@@ -995,6 +1030,8 @@ class Context(_Handle):
 
 VERIFY_SCHEDULES = {"auto": 0, "lanes": 1, "waves": 2}  # ZKFL_VERIFY_*
 ROUND_REPORT_FIELDS = ("keys", "screened", "combined", "passed", "fallback")  # zkfl_round_report
+NARROW_REPORT_FIELDS = ("keys", "screened", "combined", "passed", "groups", "bad_groups", "fallback")  # zkfl_narrow_report
+ROUND_GROUP, ROUND_NARROW_MIN = 64, 4096  # ZKFL_ROUND_GROUP, ZKFL_ROUND_NARROW_MIN
 
 
 class VerifyingKey(_Handle):
