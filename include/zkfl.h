@@ -284,8 +284,37 @@ int zkfl_debug_glv_split(const uint8_t k[32], uint8_t out[40]);
  * P_i affine std (64 B, (0, 0) = infinity), k_i 32 B std < r, out affine std (infinity = zeros) --
  * the GLV halves of k_i as two row-distributed chains, summed, affine by the divsteps inverse, as
  * k_assemble computes s pi_A + r B1 (no reference counterpart: snarkjs's G1.timesFr inside
- * groth16_prove). */
-int zkfl_debug_g1_glv_mul(zkfl_ctx* ctx, size_t n, const uint8_t* points, const uint8_t* scalars, uint8_t* out);
+ * groth16_prove).  zs: NULL, or one z_i per point (32 B std, 1 <= z_i < q): the chains then start
+ * from the XYZZ point (x z^2, y z^3, z^2, z^3), as an MSM result reaches the assembly, instead of
+ * (x, y, 1, 1).  The chains test no special case and are only right on points of the prime-order
+ * group: a point that is neither (0, 0) nor on y^2 = x^3 + 3 with x, y < q, a z outside [1, q) or a
+ * scalar >= r -> ZKFL_E_ARG, the message naming the index. */
+int zkfl_debug_g1_glv_mul(zkfl_ctx* ctx, size_t n, const uint8_t* points, const uint8_t* zs, const uint8_t* scalars,
+                          uint8_t* out);
+
+/* One operation of the assembly's field or point arithmetic on raw operands (parity hook): the
+ * 29-bit engine over Fq (nine 29-bit limbs per value, Montgomery domain 2^261), in the row policy
+ * (policy 0: csrc/row29.h RowF<P29>, a value per 16-lane row, what the GLV chains run on) or the quad
+ * policy (policy 1: Q29 of csrc/assemble.hip, a value per lane, what sums the parts).  Nothing is
+ * normalized or reduced on the way in or out: the caller chooses the lazy limbs and reads the raw
+ * result, so the operand bounds of every operation can be tested at their edges.
+ * in: n cases x 72 words, eight operands of nine limbs each (u32); out: n cases x 256 words.
+ * op (operands a0..a7):
+ *    0 mul(a0, a1)   1 add(a0, a1)   2 dbl(a0)   3..6 sub<2 | 4 | 6 | 8>(a0, a1) = a0 + K q - a1
+ *    7..10 mont<1..4> (row only): sum_k a_k a_(4+k) 2^-261, a_k replicated, a_(4+k) in row form
+ *    11..14 bcast<0..3>   15 pick4(index, a0, a1, a2, a3)   16 to(from(a0)) (row only)
+ *    17 one   18 zero   19, 20 is_zero<2 | 4>(a0)   21 canon(a0) (19..21 quad only)
+ *    32 quad_dbl(P)   33 quad_add(P, O): P = (a0, a1, a2, a3), O = (a4..a7) as X, Y, ZZ, ZZZ; the row
+ *    policy without the special cases (as the chains call them), the quad policy with them.
+ * Row policy: a wave takes four field cases, one per row (cases 4g..4g+3 share a wave: bcast<K>
+ * returns case 4g+K's operand in each of them, pick4 takes the row as index, op 16 returns row 0's
+ * value in all four), out = the row's 16 lanes (lanes 0..8 the limbs as they stand, 9..15); a point
+ * operation takes the whole wave, out = [row 0..3][X, Y, ZZ, ZZZ][16 lanes].
+ * Quad policy: four lanes per case, each storing its own result: field out = [lane 0..3][9 limbs]
+ * (bcast<K>: lane q starts from operand q; pick4 takes the lane as index; is_zero: limb 0 = 0 / 1),
+ * point out = [lane 0..3][X, Y, ZZ, ZZZ][9 limbs].  The rest of a case's 256 words is zero.
+ * n > 2^14, a null pointer, or an op the policy does not have -> ZKFL_E_ARG. */
+int zkfl_debug_asm_ops(zkfl_ctx* ctx, int policy, int op, size_t n, const uint32_t* in, uint32_t* out);
 
 /* The MSM stage of a small key's proof on a caller's sets (parity hook; a test entry: its inputs need
  * not come from a key): n1 (1..4) G1 sets sorted in the same four launches and accumulated in one

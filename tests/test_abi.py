@@ -39,6 +39,9 @@ def test_version_and_error_paths_without_device():
     one, ptr = (ctypes.c_size_t * 1)(1), (ctypes.c_char_p * 1)(bytes(buf))
     assert L.zkfl_debug_msm_front(None, 1, one, ptr, ptr, one, None, None, None, None, 0, bytes(128), 1, 1, 1,
                                   buf, (ctypes.c_uint8 * 128)()) == -1
+    words = (ctypes.c_uint32 * 256)()
+    assert L.zkfl_debug_asm_ops(None, 0, 0, 1, words, words) == -1
+    assert L.zkfl_debug_g1_glv_mul(None, 1, bytes(64), None, bytes(32), buf) == -1
 
 
 def test_glv_split_host():

@@ -1,7 +1,7 @@
 // Host-side driver for the 29-bit-limb field and point formulas (csrc/field29.h), used by
 // tests/test_field29.py: the formulas are __host__ __device__, so their bound analysis is
 // checked on the CPU against Python big integers.  One operation per stdin line:
-//   mul a b | sqr a | invb a | canon a | mulsum2 a b c d | below256 a | dbl P | madd P x y | madds P x y neg | add P Q
+//   mul a b | sqr a | invd a | canon a | mulsum2 a b c d | below256 a | dbl P | madd P x y | madds P x y neg | add P Q
 //   g2dbl P | g2madd P x y | g2add P Q   (Fq2 values as two elements: c0 c1)
 //   rmul a b | rsqr a | radd a b | rmulsum4 x0 x1 x2 x3 y0 y1 y2 y3 | rfromplain a | rtoplain a |
 //   rfrom256 a | rto256 a   (Fr in the witness engine's 29-bit form, csrc/fr29.h)

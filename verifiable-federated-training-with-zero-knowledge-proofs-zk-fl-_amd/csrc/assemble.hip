@@ -48,7 +48,11 @@ __device__ void store_affine_std<Fq2Ops>(const Affine<Fq2Ops>& a, uint32_t* out)
 // column chains: ~2.5x shorter single-lane latency than the 32-bit fp_mul).  Values are LAZY
 // (normalized limbs, below a small multiple of p, tracked per site in the formulas' comments):
 //   mul(a, b) < p + a b / 2^261 < 2p whenever a b < 169 p^2 (2^261 ~ 169.3 p);
-//   add(a, b) < bound(a) + bound(b);  sub<K>(a, b) = a + K p - b for b < K p, < bound(a) + K p;
+//   add(a, b) < bound(a) + bound(b);  sub<K>(a, b) = a + K p - b < bound(a) + K p, for b <= a + K p
+//   on Q29 but only for a + K p - b >= 2^206 on the row policy (row29.h: its top lane wraps below
+//   that), so every site keeps its subtrahend well below K p: a product is < p + a b / 2^261, and
+//   the formulas' comments give the bound of each subtrahend (tests/test_row_bounds_cpu.py walks
+//   them; the narrowest site keeps 0.87 p);
 //   is_zero<K>(a) for a < K p (a == 0, p, .., (K-1) p).
 // A quad operation keeps X < 8p, Y < 4p, ZZ, ZZZ < 2p (in and out), so no product or sum is
 // brought below p on the chain: the canonical (< p) form is taken once, when a point leaves
@@ -154,8 +158,11 @@ ZK_DEV G1P g1q_to(const G1Q& p) {  // canonical coordinates out
 }
 
 // dbl-2008-s-1 by levels: {U^2, X^2} -> {U V, X V, V ZZ, M^2} -> {M (S - X3), W Y, W ZZZ}
-// Bounds (X < 8p, Y < 4p, ZZ, ZZZ < 2p in): U < 8p; V, X2 < 2p (64 p^2); M < 6p; W, S, ZZ3, M2
-// < 2p (36 p^2); X3 < 6p; S - X3 < 8p; Y3's products < 2p (48 p^2), Y3 < 4p.
+// Bounds (X < 8p, Y < 4p, ZZ, ZZZ < 2p in; 2^261 = 169.3 p): U < 8p; V, X2 < 1.38p (64 p^2);
+// M < 4.14p; W, S < 1.07p, ZZ3 < 1.02p, M2 < 1.11p; X3 = M2 + 4p - 2S with 2S < 2.14p, X3 < 5.11p;
+// S + 6p - X3 < 5.20p (X3 > 1.86p); Y3's products M (S - X3) < 1.13p and W Y < 1.03p, Y3 < 3.13p;
+// ZZZ3 < 1.02p.
+// Every difference stays above 0.89p (sub<K>'s precondition on the row policy).
 // CHECK = false: the operands are known to be finite and distinct (the row chains of glv_row_mul),
 // so the special cases are not tested (the row policy has no is_zero)
 template <class QF, bool CHECK = true>
@@ -183,9 +190,11 @@ ZK_DEV QPoint<QF> quad_dbl(const QPoint<QF>& p, int q) {
 
 // add-2008-s by levels: {U1, U2, S1, S2} -> {P^2, R^2, ZZ1 ZZ2, ZZZ1 ZZZ2} -> {P PP, U1 PP, ZZ PP}
 // -> {R (Q - X3), S1 PPP, ZZZ PPP}
-// Bounds (both points X < 8p, Y < 4p, ZZ, ZZZ < 2p): U1, U2, S1, S2 < 2p (16 p^2); P, R < 4p;
-// PP, R2, Z12, ZZZ12 < 2p; PPP, Q, ZZ3 < 2p; X3 < 8p; Q - X3 < 10p; Y3's products < 2p
-// (40 p^2), Y3 < 4p.
+// Bounds (both points X < 8p, Y < 4p, ZZ, ZZZ < 2p): U1, U2 < 1.10p (16 p^2), S1, S2 < 1.05p;
+// P < 3.10p, R < 3.05p; PP, R2 < 1.06p, Z12, ZZZ12 < 1.03p; PPP < 1.02p, Q, ZZ3 < 1.01p;
+// R2 + 2p - PPP in (0.98p, 3.06p), X3 = that + 4p - 2Q in (2.96p, 7.06p); Q + 8p - X3 < 6.05p; Y3's
+// products R (Q - X3) < 1.11p and S1 PPP < 1.01p, Y3 < 3.11p; ZZZ3 < 1.01p.  Every difference stays above
+// 0.90p (sub<K>'s precondition on the row policy).
 template <class QF, bool CHECK = true>
 ZK_DEV QPoint<QF> quad_add(const QPoint<QF>& p, const QPoint<QF>& o, int q) {
   using T = typename QF::T;
@@ -316,7 +325,9 @@ ZK_DEV G1Q glv_row_mul(const G1P* __restrict__ res, const GlvScalar* __restrict_
       const int e = (d < 0 ? -d : d) - 1;
       RPt t = {{tab[(4 * e + 0) * 64 + lane]}, {tab[(4 * e + 1) * 64 + lane]}, {tab[(4 * e + 2) * 64 + lane]},
                {tab[(4 * e + 3) * 64 + lane]}};
-      if (d < 0) t.Y = Row29::sub<4>(Row29::zero(), t.Y);  // Y < 4p
+      // a table entry's Y is the canonical input or a quad_dbl / quad_add output: 0 < Y < 3.13p, so
+      // 4p - Y is in (0.87p, 4p) -- Y < 4p alone would not keep sub<4> above its precondition
+      if (d < 0) t.Y = Row29::sub<4>(Row29::zero(), t.Y);
       if (inf)
         acc = t;
       else
@@ -417,8 +428,10 @@ __global__ void __launch_bounds__(ASM_T_THREADS) k_assemble_t(G1P* __restrict__ 
 // Parity hook for the assembly's scalar multiplications (zkfl_debug_g1_glv_mul): block b computes
 // k_b P_b as k_assemble computes s pi_A' -- two row chains (glv_row_mul over (k1, P) and
 // (k2, phi(P)), the GLV halves of k), their sum by a quad addition, affine by the divsteps inverse.
-// pts: affine std (x, y), (0, 0) = infinity; out: affine std, infinity as zeros.
-__global__ void __launch_bounds__(128) k_debug_glv_mul(const uint32_t* __restrict__ pts,
+// pts: affine std (x, y), (0, 0) = infinity; zs: NULL, or one z (std, nonzero) per point: the
+// chains then start from (x z^2, y z^3, z^2, z^3), as an MSM result arrives, instead of (x, y, 1, 1);
+// out: affine std, infinity as zeros.
+__global__ void __launch_bounds__(128) k_debug_glv_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ zs,
                                                        const GlvScalar* __restrict__ ks, uint32_t* __restrict__ out) {
   const uint32_t* pa = pts + 16 * blockIdx.x;
   ks += 2 * blockIdx.x;
@@ -435,6 +448,13 @@ __global__ void __launch_bounds__(128) k_debug_glv_mul(const uint32_t* __restric
       z |= x.v[i] | y.v[i];
     }
     P = z ? G1P{fp_to_mont(x), fp_to_mont(y), fp_one<FqP>(), fp_one<FqP>()} : xyzz_inf<FqOps>();
+    if (z && zs) {
+      Fq zv;
+      for (int i = 0; i < 8; i++) zv.v[i] = zs[8 * blockIdx.x + i];
+      zv = fp_to_mont(zv);
+      const Fq zz = fp_sqr(zv), zzz = fp_mul(zz, zv);
+      P = G1P{fp_mul(P.X, zz), fp_mul(P.Y, zzz), zz, zzz};
+    }
   }
   __syncthreads();
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
@@ -445,6 +465,135 @@ __global__ void __launch_bounds__(128) k_debug_glv_mul(const uint32_t* __restric
     const G1Q S = quad_add<Q29>(part[0], part[1], lane & 3);
     if (lane == 0) store_affine_std<FqOps>(g1_to_affine29(g1q_to(S)), out);
   }
+}
+
+// Parity hook for the field and point layers of both policies (zkfl_debug_asm_ops): one operation on
+// the caller's raw limbs, nothing normalized or reduced on the way in or out.  in: ASM_DBG_IN words
+// per case, eight operands of nine limbs (a point is four: X, Y, ZZ, ZZZ); out: ASM_DBG_OUT words
+// per case (the layouts: assemble.h).
+// Row policy: a wave takes four cases of a field operation, one per row, so the four rows are live at
+// once and differ; or one case of a point operation, every row holding the point and computing its
+// share of the products, as in glv_row_mul (CHECK = false).  All 64 lanes stay active (a case past n
+// computes on zeros and stores nothing): the DPP moves and the row swaps read across lanes.
+template <class RF, int K>
+ZK_DEV typename RF::T dbg_row_mont(const uint32_t* ci, bool live, uint32_t j) {
+  uint32_t a[K][9], b[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) a[k][i] = live ? ci[9 * k + i] : 0u;
+    b[k] = live && j < 9 ? ci[9 * (4 + k) + j] : 0u;
+  }
+  return RF::template mont<K>(a, b);
+}
+
+template <class RF>
+__global__ void __launch_bounds__(64) k_debug_asm_row(int op, uint32_t n, const uint32_t* __restrict__ in,
+                                                      uint32_t* __restrict__ out) {
+  using T = typename RF::T;
+  const int lane = threadIdx.x, q = lane >> 4;
+  const uint32_t j = lane & 15;
+  const bool point = op >= ASM_OP_PDBL;
+  const uint32_t c = point ? blockIdx.x : 4 * blockIdx.x + q;
+  const bool live = c < n;
+  const uint32_t* ci = in + (size_t)ASM_DBG_IN * (live ? c : 0);
+  uint32_t* co = out + (size_t)ASM_DBG_OUT * (live ? c : 0);
+  auto ld = [&](int k) -> T { return {live && j < 9 ? ci[9 * k + j] : 0u}; };
+  if (point) {
+    const QPoint<RF> p = {ld(0), ld(1), ld(2), ld(3)}, o = {ld(4), ld(5), ld(6), ld(7)};
+    const QPoint<RF> r = op == ASM_OP_PDBL ? quad_dbl<RF, false>(p, q) : quad_add<RF, false>(p, o, q);
+    if (live) {
+      co[64 * q + j] = r.X.v;
+      co[64 * q + 16 + j] = r.Y.v;
+      co[64 * q + 32 + j] = r.ZZ.v;
+      co[64 * q + 48 + j] = r.ZZZ.v;
+    }
+    return;
+  }
+  T r = RF::zero();
+  switch (op) {
+    case ASM_OP_MUL: r = RF::mul(ld(0), ld(1)); break;
+    case ASM_OP_ADD: r = RF::add(ld(0), ld(1)); break;
+    case ASM_OP_DBL: r = RF::dbl(ld(0)); break;
+    case ASM_OP_SUB2: r = RF::template sub<2>(ld(0), ld(1)); break;
+    case ASM_OP_SUB4: r = RF::template sub<4>(ld(0), ld(1)); break;
+    case ASM_OP_SUB6: r = RF::template sub<6>(ld(0), ld(1)); break;
+    case ASM_OP_SUB8: r = RF::template sub<8>(ld(0), ld(1)); break;
+    case ASM_OP_MONT1: r = dbg_row_mont<RF, 1>(ci, live, j); break;
+    case ASM_OP_MONT2: r = dbg_row_mont<RF, 2>(ci, live, j); break;
+    case ASM_OP_MONT3: r = dbg_row_mont<RF, 3>(ci, live, j); break;
+    case ASM_OP_MONT4: r = dbg_row_mont<RF, 4>(ci, live, j); break;
+    case ASM_OP_BCAST0: r = RF::template bcast<0>(ld(0)); break;
+    case ASM_OP_BCAST1: r = RF::template bcast<1>(ld(0)); break;
+    case ASM_OP_BCAST2: r = RF::template bcast<2>(ld(0)); break;
+    case ASM_OP_BCAST3: r = RF::template bcast<3>(ld(0)); break;
+    case ASM_OP_PICK4: r = RF::pick4(q, ld(0), ld(1), ld(2), ld(3)); break;
+    case ASM_OP_FROM_TO: {  // to() reads row 0: every row of the wave returns row 0's value
+      F29 x;
+#pragma unroll
+      for (int i = 0; i < 9; i++) x.v[i] = live ? ci[i] : 0u;
+      const F29 y = RF::to(RF::from(x));
+#pragma unroll
+      for (int i = 0; i < 9; i++) r.v = j == (uint32_t)i ? y.v[i] : r.v;
+      break;
+    }
+    case ASM_OP_ONE: r = RF::one(); break;
+    default: break;  // ASM_OP_ZERO
+  }
+  if (live) co[j] = r.v;
+}
+
+// Quad policy: four lanes per case (lane q of the quad is quad index q), sixteen cases per wave; every
+// lane stores its own result, so the hook also shows that the four lanes of a quad agree.  Point
+// operations run with CHECK = true, as asm_pair_sums and k_assemble call them.
+__global__ void __launch_bounds__(64) k_debug_asm_quad(int op, uint32_t n, const uint32_t* __restrict__ in,
+                                                       uint32_t* __restrict__ out) {
+  const int lane = threadIdx.x, q = lane & 3;
+  const uint32_t c = 16 * blockIdx.x + (lane >> 2);
+  const bool live = c < n;
+  const uint32_t* ci = in + (size_t)ASM_DBG_IN * (live ? c : 0);
+  uint32_t* co = out + (size_t)ASM_DBG_OUT * (live ? c : 0);
+  auto ld = [&](int k) {
+    F29 r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.v[i] = live ? ci[9 * k + i] : 0u;
+    return r;
+  };
+  if (op >= ASM_OP_PDBL) {
+    const G1Q p = {ld(0), ld(1), ld(2), ld(3)}, o = {ld(4), ld(5), ld(6), ld(7)};
+    const G1Q r = op == ASM_OP_PDBL ? quad_dbl<Q29>(p, q) : quad_add<Q29>(p, o, q);
+    if (live) {
+      for (int i = 0; i < 9; i++) {
+        co[36 * q + i] = r.X.v[i];
+        co[36 * q + 9 + i] = r.Y.v[i];
+        co[36 * q + 18 + i] = r.ZZ.v[i];
+        co[36 * q + 27 + i] = r.ZZZ.v[i];
+      }
+    }
+    return;
+  }
+  F29 r = f29_zero();
+  switch (op) {
+    case ASM_OP_MUL: r = Q29::mul(ld(0), ld(1)); break;
+    case ASM_OP_ADD: r = Q29::add(ld(0), ld(1)); break;
+    case ASM_OP_DBL: r = Q29::dbl(ld(0)); break;
+    case ASM_OP_SUB2: r = Q29::sub<2>(ld(0), ld(1)); break;
+    case ASM_OP_SUB4: r = Q29::sub<4>(ld(0), ld(1)); break;
+    case ASM_OP_SUB6: r = Q29::sub<6>(ld(0), ld(1)); break;
+    case ASM_OP_SUB8: r = Q29::sub<8>(ld(0), ld(1)); break;
+    case ASM_OP_BCAST0: r = Q29::bcast<0>(ld(q)); break;  // lane q of the quad holds operand q
+    case ASM_OP_BCAST1: r = Q29::bcast<1>(ld(q)); break;
+    case ASM_OP_BCAST2: r = Q29::bcast<2>(ld(q)); break;
+    case ASM_OP_BCAST3: r = Q29::bcast<3>(ld(q)); break;
+    case ASM_OP_PICK4: r = Q29::pick4(q, ld(0), ld(1), ld(2), ld(3)); break;
+    case ASM_OP_ONE: r = Q29::one(); break;
+    case ASM_OP_IS_ZERO2: r.v[0] = Q29::is_zero<2>(ld(0)) ? 1u : 0u; break;
+    case ASM_OP_IS_ZERO4: r.v[0] = Q29::is_zero<4>(ld(0)) ? 1u : 0u; break;
+    case ASM_OP_CANON: r = Q29::canon(ld(0)); break;
+    default: break;  // ASM_OP_ZERO
+  }
+  if (live)
+    for (int i = 0; i < 9; i++) co[9 * q + i] = r.v[i];
 }
 
 __global__ void __launch_bounds__(128) k_assemble_c(const G1P* __restrict__ res, const G2P* __restrict__ resB2,
@@ -591,8 +740,26 @@ void assemble_c(hipStream_t st, const G1P* res, const G2P* resB2, uint32_t* proo
 
 void fold_a(hipStream_t st, G1P* res) { hipLaunchKernelGGL(k_fold_a, dim3(1), dim3(64), 0, st, res); }
 
-void debug_glv_mul(hipStream_t st, uint32_t n, const uint32_t* pts, const GlvScalar* ks, uint32_t* out) {
-  hipLaunchKernelGGL(k_debug_glv_mul, dim3(n), dim3(128), 0, st, pts, ks, out);
+void debug_glv_mul(hipStream_t st, uint32_t n, const uint32_t* pts, const uint32_t* zs, const GlvScalar* ks,
+                   uint32_t* out) {
+  hipLaunchKernelGGL(k_debug_glv_mul, dim3(n), dim3(128), 0, st, pts, zs, ks, out);
+}
+
+bool debug_asm_op_ok(int policy, int op) {
+  if (op == ASM_OP_PDBL || op == ASM_OP_PADD) return policy == 0 || policy == 1;
+  if (policy == 0) return op >= ASM_OP_MUL && op <= ASM_OP_ZERO;
+  if (policy == 1)  // no mont<K> and no row form on one lane
+    return op >= ASM_OP_MUL && op <= ASM_OP_CANON && !(op >= ASM_OP_MONT1 && op <= ASM_OP_MONT4) &&
+           op != ASM_OP_FROM_TO;
+  return false;
+}
+
+void debug_asm_ops(hipStream_t st, int policy, int op, uint32_t n, const uint32_t* in, uint32_t* out) {
+  const bool point = op >= ASM_OP_PDBL;
+  if (policy == 0)
+    hipLaunchKernelGGL(k_debug_asm_row<Row29>, dim3(point ? n : (n + 3) / 4), dim3(64), 0, st, op, n, in, out);
+  else
+    hipLaunchKernelGGL(k_debug_asm_quad, dim3((n + 15) / 16), dim3(64), 0, st, op, n, in, out);
 }
 
 void part_out(hipStream_t st, const G1P* res, const G2P* resB2, uint32_t* out) {

@@ -11,6 +11,17 @@
 // per row) per wave at a fraction of a one-lane product's latency.  Values cross rows by the gfx950
 // row swaps (bcast<K>).  Limbs are lazy: lanes 0..7 below 2^29 + 2^7 (one or two carry-save steps
 // per operation), lane 8 the exact top; the integer bounds are those of the one-lane formulas.
+//
+// Precondition of sub<K>(a, b) = a + K M - b.  Lanes 0..7 of a + row_kp(K) - b stay inside 32 bits
+// for any lazy a, b, but lane 8 holds a8 + (K M)8 - 4 - b8 modulo 2^32 and receives
+// 4 + floor((s7 - 4) / 2^29) from lane 7 (s7 = a7 + (K M)7 - b7): it ends below zero -- wrapped, the
+// unsigned limb sum off by 2^264 -- exactly when 2^29 (a8 + (K M)8 - b8) + s7 <= 3.  In terms of the
+// integer D = a + K M - b: the result is exact for every lazy a, b with
+//   D >= 3 2^203 + sum_{j<7} (2^29 + 2^7 - 1 + (K M)_j) 2^(29 j) + 1      (< 2^206 for every K),
+// and below that some limb patterns wrap (D = 1 from normalized operands does).  b < K M is NOT
+// enough.  The point formulas keep D above 0.87 M at every site because a product is
+// < M + a b / 2^261, far below the K M it is subtracted from (tests/test_row_bounds_cpu.py walks
+// the sites; tests/test_gpu_asm_arith.py runs both sides' operands through the kernels).
 #pragma once
 #include "field29.h"
 
@@ -42,7 +53,8 @@ __host__ __device__ constexpr Limbs9 m29_one() {
   return Limbs9{{M::ONE[0], M::ONE[1], M::ONE[2], M::ONE[3], M::ONE[4], M::ONE[5], M::ONE[6], M::ONE[7], M::ONE[8]}};
 }
 // k M + 2^31 (limbs 0..7) - 4 (limbs 1..8): a + this - b keeps every lane in [0, 2^32) for lazy b
-// (limbs < 2^29 + 2^7); the top limb may wrap below zero and is made whole by the carries
+// (limbs < 2^29 + 2^7); the top limb may wrap below zero and is made whole by the carries when
+// a + k M - b is at least 2^206 (sub<K>'s precondition, above)
 template <class M>
 __host__ __device__ constexpr Limbs9 row_kp(uint32_t k) {
   Limbs9 r = m29_times<M>(k, false);

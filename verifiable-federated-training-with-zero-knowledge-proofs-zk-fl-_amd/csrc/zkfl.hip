@@ -32,6 +32,7 @@
 
 #include "assemble.h"
 #include "devbufs.h"
+#include "field29.h"
 #include "glv.h"
 #include "host_parse.h"
 #include "merkle.h"
@@ -130,6 +131,34 @@ int tree_from_device_leaves(zkfl_ctx* ctx, DevBufs& B, const Fr* d_leaves, size_
   return ZKFL_OK;
 }
 
+// Host checks of a parity hook's Fq inputs (std, 8 x 32-bit words), on the 29-bit engine's
+// host-callable code: w < q
+bool fq_words_lt_p(const uint32_t (&w)[8]) {
+  const F29 a = f29_pack(w), c = f29_canon_sub<1>(a);  // a < 2^256 < 6q: unchanged exactly when a < q
+  uint32_t d = 0;
+  for (int i = 0; i < 9; i++) d |= a.v[i] ^ c.v[i];
+  return d == 0;
+}
+// (x, y) is (0, 0), or x, y < q and y^2 = x^3 + 3.  A product is a b 2^-261 mod q, so both sides are
+// taken times 2^-522: (y y) 1, (x x) x, (3 1) 1; each < 1.01 q, the right side's sum < 2.02 q.
+bool g1_std_ok(const uint32_t (&x)[8], const uint32_t (&y)[8]) {
+  uint32_t nz = 0;
+  for (int i = 0; i < 8; i++) nz |= x[i] | y[i];
+  if (!nz) return true;
+  if (!fq_words_lt_p(x) || !fq_words_lt_p(y)) return false;
+  const F29 X = f29_pack(x), Y = f29_pack(y);
+  F29 one = f29_zero(), three = f29_zero();
+  one.v[0] = 1;
+  three.v[0] = 3;
+  const F29 lhs = f29_canon_sub<1>(f29_mul(f29_mul(Y, Y), one));
+  F29 rhs = f29_add_lazy(f29_mul(f29_mul(X, X), X), f29_mul(f29_mul(three, one), one));
+  f29_norm(rhs);
+  rhs = f29_canon_sub<2>(rhs);
+  uint32_t d = 0;
+  for (int i = 0; i < 9; i++) d |= lhs.v[i] ^ rhs.v[i];
+  return d == 0;
+}
+
 int tree_args(zkfl_ctx* ctx, size_t n, uint32_t depth, const void* in, const void* out) {
   if (!ctx || !out || (n && !in)) return fail(ZKFL_E_ARG, "merkle: null argument");
   if (depth > ZKFL_MERKLE_MAX_DEPTH) return fail(ZKFL_E_ARG, "merkle: depth must be <= 30");
@@ -185,31 +214,68 @@ int zkfl_debug_glv_split(const uint8_t k[32], uint8_t out[40]) {
   return ZKFL_OK;
 }
 
-int zkfl_debug_g1_glv_mul(zkfl_ctx* ctx, size_t n, const uint8_t* points, const uint8_t* scalars, uint8_t* out) {
+int zkfl_debug_g1_glv_mul(zkfl_ctx* ctx, size_t n, const uint8_t* points, const uint8_t* zs, const uint8_t* scalars,
+                          uint8_t* out) {
   if (!ctx || (n && (!points || !scalars || !out))) return fail(ZKFL_E_ARG, "null argument");
   if (n == 0) return ZKFL_OK;
   if (n > (1u << 20)) return fail(ZKFL_E_ARG, "glv mul: n too large");
   std::vector<GlvScalar> ks(2 * n);
   for (size_t i = 0; i < n; i++) {
-    uint32_t kk[8];
+    uint32_t kk[8], x[8], y[8];
     memcpy(kk, scalars + 32 * i, 32);
     if (!fr_lt_r(kk)) return fail(ZKFL_E_ARG, "glv mul: scalar " + std::to_string(i) + " is not < r");
     glv_split(kk, ks[2 * i], ks[2 * i + 1]);
+    // the chains test no special case: they are only right on the curve's (prime-order) points
+    memcpy(x, points + 64 * i, 32);
+    memcpy(y, points + 64 * i + 32, 32);
+    if (!g1_std_ok(x, y))
+      return fail(ZKFL_E_ARG, "glv mul: point " + std::to_string(i) + " is neither (0, 0) nor on the curve");
+    if (zs) {
+      memcpy(x, zs + 32 * i, 32);
+      uint32_t nz = 0;
+      for (int k = 0; k < 8; k++) nz |= x[k];
+      if (!nz || !fq_words_lt_p(x)) return fail(ZKFL_E_ARG, "glv mul: z " + std::to_string(i) + " is not in [1, q)");
+    }
   }
   HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
   hipStream_t st = ctx->st;
   DevBufs D;
-  uint32_t *d_p, *d_o;
+  uint32_t *d_p, *d_o, *d_z = nullptr;
   GlvScalar* d_k;
   HIP_TRY(D.get(&d_p, n * 16), "glv mul");
   HIP_TRY(D.get(&d_k, ks.size()), "glv mul");
   HIP_TRY(D.get(&d_o, n * 16), "glv mul");
   HIP_TRY(hipMemcpyAsync(d_p, points, n * 64, hipMemcpyHostToDevice, st), "glv mul");
+  if (zs) {
+    HIP_TRY(D.get(&d_z, n * 8), "glv mul");
+    HIP_TRY(hipMemcpyAsync(d_z, zs, n * 32, hipMemcpyHostToDevice, st), "glv mul");
+  }
   HIP_TRY(hipMemcpyAsync(d_k, ks.data(), ks.size() * sizeof(GlvScalar), hipMemcpyHostToDevice, st), "glv mul");
-  debug_glv_mul(st, (uint32_t)n, d_p, d_k, d_o);
+  debug_glv_mul(st, (uint32_t)n, d_p, d_z, d_k, d_o);
   HIP_TRY(hipGetLastError(), "glv mul");
   HIP_TRY(hipMemcpyAsync(out, d_o, n * 64, hipMemcpyDeviceToHost, st), "glv mul");
   HIP_TRY(hipStreamSynchronize(st), "glv mul");
+  return ZKFL_OK;
+}
+
+int zkfl_debug_asm_ops(zkfl_ctx* ctx, int policy, int op, size_t n, const uint32_t* in, uint32_t* out) {
+  if (!ctx || (n && (!in || !out))) return fail(ZKFL_E_ARG, "asm ops: null argument");
+  if (!debug_asm_op_ok(policy, op))
+    return fail(ZKFL_E_ARG, "asm ops: no operation " + std::to_string(op) + " in policy " + std::to_string(policy));
+  if (n == 0) return ZKFL_OK;
+  if (n > (1u << 14)) return fail(ZKFL_E_ARG, "asm ops: n too large (at most 2^14 cases)");
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = ctx->st;
+  DevBufs D;
+  uint32_t *d_i, *d_o;
+  HIP_TRY(D.get(&d_i, n * ASM_DBG_IN), "asm ops");
+  HIP_TRY(D.get(&d_o, n * ASM_DBG_OUT), "asm ops");
+  HIP_TRY(hipMemcpyAsync(d_i, in, n * ASM_DBG_IN * 4, hipMemcpyHostToDevice, st), "asm ops");
+  HIP_TRY(hipMemsetAsync(d_o, 0, n * ASM_DBG_OUT * 4, st), "asm ops");
+  debug_asm_ops(st, policy, op, (uint32_t)n, d_i, d_o);
+  HIP_TRY(hipGetLastError(), "asm ops");
+  HIP_TRY(hipMemcpyAsync(out, d_o, n * ASM_DBG_OUT * 4, hipMemcpyDeviceToHost, st), "asm ops");
+  HIP_TRY(hipStreamSynchronize(st), "asm ops");
   return ZKFL_OK;
 }
 

@@ -208,7 +208,9 @@ SIGNATURES = {
     "zkfl_groth16_prove_batch": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(_P), C.c_char_p, _U8P]),
     "zkfl_debug_prove_parts": (C.c_int, [_P, _P, C.c_char_p, C.c_size_t, _U8P, _U8P]),
     "zkfl_debug_glv_split": (C.c_int, [C.c_char_p, _U8P]),
-    "zkfl_debug_g1_glv_mul": (C.c_int, [_P, C.c_size_t, C.c_char_p, C.c_char_p, _U8P]),
+    "zkfl_debug_g1_glv_mul": (C.c_int, [_P, C.c_size_t, C.c_char_p, C.c_char_p, C.c_char_p, _U8P]),
+    "zkfl_debug_asm_ops": (C.c_int, [_P, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint32)]),
     "zkfl_debug_msm_front": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_char_p),
                                        C.POINTER(C.c_char_p), C.POINTER(C.c_size_t),
                                        C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32), C.POINTER(C.c_char_p),
@@ -521,13 +523,32 @@ class Context(_Handle):
         check(lib().zkfl_msm_g1(self.h, bases, scalars, n, out))
         return bytes(out)
 
-    def g1_glv_mul(self, points: bytes, scalars: bytes) -> bytes:
-        """The assembly's scalar multiplications (parity hook): k_i P_i, affine std in and out."""
+    def g1_glv_mul(self, points: bytes, scalars: bytes, zs: bytes | None = None) -> bytes:
+        """The assembly's scalar multiplications (parity hook): k_i P_i, affine std in and out.
+        zs: one z per point (32 B std, nonzero): the chains start from (x z^2, y z^3, z^2, z^3)."""
         n = len(scalars) // 32
-        assert len(points) == 64 * n
+        assert len(points) == 64 * n and (zs is None or len(zs) == 32 * n)
         out = _buf(64 * n)
-        check(lib().zkfl_debug_g1_glv_mul(self.h, n, points, scalars, out))
+        check(lib().zkfl_debug_g1_glv_mul(self.h, n, points, zs, scalars, out))
         return bytes(out)
+
+    ASM_IN, ASM_OUT = 72, 256   # words per case of asm_ops
+
+    def asm_ops(self, policy: int, op: int, cases) -> list:
+        """One operation of the assembly's field / point arithmetic on raw limbs (parity hook,
+        zkfl_debug_asm_ops; include/zkfl.h lists the operations and layouts).  policy 0: row, 1: quad;
+        cases: per case up to eight operands of nine u32 limbs.  -> per case its 256 output words."""
+        n = len(cases)
+        inp = (C.c_uint32 * (self.ASM_IN * n))()
+        for c, ops in enumerate(cases):
+            assert len(ops) <= 8
+            for k, limbs in enumerate(ops):
+                assert len(limbs) == 9
+                inp[self.ASM_IN * c + 9 * k:self.ASM_IN * c + 9 * k + 9] = [int(v) for v in limbs]
+        out = (C.c_uint32 * (self.ASM_OUT * n))()
+        check(lib().zkfl_debug_asm_ops(self.h, policy, op, n, inp, out))
+        flat = list(out)
+        return [flat[self.ASM_OUT * c:self.ASM_OUT * (c + 1)] for c in range(n)]
 
     def msm_front(self, sets, b: int, bases_g2: bytes, fast: bool = True, joint: bool = True):
         """The MSM stage of a small key's proof on the caller's sets (parity hook,
